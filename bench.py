@@ -8,9 +8,13 @@ all-reduce of (sum nll, count), the only exchange the path has.
 Workload: BASELINE config 3's flow (8-layer MAF-RQS, D=15, C=288, H=256, K=16,
 tail_bound 5) at batch 4096 PER GPU (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline     achieved = batch * dense-GEMM FLOP/sample / avg kernel time (HIP events)
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and
+prints the headline figure (value, ms_per_step, config); --dump-outputs DIR also writes what the last timed step
+computed.  Everything that takes runs of its own is behind --full:
+  roofline     achieved = batch * dense-GEMM FLOP/sample / avg kernel time (HIP events), the per-CU ingest floor
   cpu_baseline the CPU oracle (reference algorithm, fp32, all host cores) on the same batch
+  parity       the GPU's nll of the timed batch against that oracle and a float64 evaluation of it
+  extras       other precisions, sizes and configurations (sampling, encoder, training step, ...)
 """
 import argparse
 import json
@@ -547,6 +551,24 @@ def config4_train_step(dev, precision, events=1024, reps=5):
     return {f"train_step_ms_{events}": dt * 1e3, f"train_events_per_s_{events}": events / dt}
 
 
+DUMP_CAP_BYTES = 48 << 20     # --dump-outputs writes at most this much over all ranks (the limit is 64 MB)
+
+
+def dump_outputs(path, rank, world, nll, sum_count):
+    """--dump-outputs: what the last timed step handed its caller -- the per-row nll of this rank's batch (float32) and,
+    on the collective path, the all-reduced (sum nll, rows) pair (float64, rank 0) -- as <name>.npy under `path`.
+    A batch beyond the size cap is written as a fixed, seeded sample of its rows (ascending row order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = nll.detach().float().cpu()
+    cap = DUMP_CAP_BYTES // 4 // world
+    if out.numel() > cap:
+        out = out[torch.randperm(out.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values]
+    np.save(os.path.join(path, f"nll_rank{rank}.npy" if world > 1 else "nll.npy"), out.numpy())
+    if sum_count is not None and rank == 0:
+        np.save(os.path.join(path, "sum_count.npy"), sum_count.numpy())
+
+
 def pmc_traffic(args):
     """bytes per launch at the L2's memory side from the committed PMC passes of the build being timed (rocprofv3
     cannot run inside this process): only for the configuration they were collected on, else null."""
@@ -580,8 +602,14 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--graph", action="store_true", help="N = 1: replay one HIP graph per step instead of one pre-bound launch")
     ap.add_argument("--no-graph", action="store_true", help="(default now; kept for older command lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sampling / embedding side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline figure: kernel-only "
+                         "time and roofline, ingest floor, extras, CPU baseline, parity (each takes runs of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (nll per row; on the "
+                         "collective path also the all-reduced sum_count); the inputs are the same in every run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the sampling / embedding side measurements")
     ap.add_argument("--collective", action="store_true", help="run the N > 1 step (with its all-reduce) on a single rank")
     ap.add_argument("--allreduce-every", type=int, default=1,
                     help="N > 1: steps per all-reduce of the in-kernel (sum nll, rows) accumulator (1 = every step, the "
@@ -724,12 +752,14 @@ def main():
             run()
         elapsed, dev_ms = timed_loop(run, args.steps)
         log(f"timed {args.steps} steps: {elapsed * 1e3 / args.steps:.4f} ms/step (device {dev_ms / args.steps:.4f})")
-        mean_nll = None
+        mean_nll = last = None
         if collective:
             last = red[state["last"]].double().sum(0).cpu()   # (sum nll, count) of the last window over all ranks and slots
             mean_nll = (last[0] / last[1]).item()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, world, nll, last)
         windowed = None
-        if collective and state["M"] == 1:               # beside the contract number: one all-reduce per 16 steps
+        if args.full and collective and state["M"] == 1:   # beside the contract number: one all-reduce per 16 steps
             state["M"], state["k"] = 16, 0
             for i in range(NBUF):
                 red[i].zero_()
@@ -739,21 +769,13 @@ def main():
             windowed = world * args.batch * args.steps / el16
             state["M"] = 1
 
-    kernel_ms = kernel_time_ms(flow, x, ctx, nll, stream, max(20, min(args.steps, 200)))
-    log(f"kernel-only: {kernel_ms * 1e3:.2f} us")
+    kernel_ms = None
+    if args.full:
+        kernel_ms = kernel_time_ms(flow, x, ctx, nll, stream, max(20, min(args.steps, 200)))
+        log(f"kernel-only: {kernel_ms * 1e3:.2f} us")
 
     if rank == 0:
-        fl = flops_per_sample()
-        ach = args.batch * fl / (kernel_ms * 1e-3) / 1e12
-        peak = PEAK_TFLOPS[args.precision]
         lib = __import__("posteriflow_amd")._lib.lib()
-        # the three FLOP conventions side by side: `achieved` / `frac` use SURVEY 8d's ALGORITHMIC dense-GEMM count (the
-        # contract's figure: masks not discounted); the MFMAs the dispatched kernel really issues multiply the packed stream,
-        # in which all-zero fragments of the autoregressive masks do not exist (pf_flow_issued_flop_per_row), and the useful
-        # share of those is the mask-aware count
-        fl_issued = int(lib.pf_flow_issued_flop_per_row(flow._desc(wide=flow._use_wide(args.batch))))
-        fl_masked = masked_flops_per_sample()
-        tf = lambda f: args.batch * f / (kernel_ms * 1e-3) / 1e12
         out = {
             "metric": "flow.log_prob samples/sec at batch 4096",
             "value": world * args.batch * args.steps / elapsed,
@@ -775,41 +797,52 @@ def main():
                        "settle": max(0, args.settle),   # untimed clock-settling launches in front of the W warm-up steps
                        "global_mean_nll": mean_nll,
                        "parallelism": f"dp{world}"},
-            "roofline": {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
-                         "frac": ach / peak, "traffic": pmc_traffic(args),
-                         "kernel": flow.forward_kernel_name(args.batch), "kernel_ms": kernel_ms,
-                         "flop_convention": "achieved/frac: SURVEY 8d dense-GEMM count (masked zeros counted); *_issued: "
-                                            "MFMAs the kernel executes (mask-compressed stream); *_mask_aware: useful FLOP only",
-                         "flop_per_sample": fl, "flop_per_sample_issued": fl_issued, "flop_per_sample_mask_aware": fl_masked,
-                         "achieved_issued": tf(fl_issued), "frac_issued": tf(fl_issued) / peak,
-                         "achieved_mask_aware": tf(fl_masked), "frac_mask_aware": tf(fl_masked) / peak,
-                         "device_ms_per_step": dev_ms / args.steps},
         }
-        if world == 1 and args.batch <= 20479:
-            # the bound this design actually has at 16 rows per workgroup: every workgroup ingests the whole packed stream
-            floor_us, nbytes, wgs = ingest_floor_us(flow, args.batch, dev, stream)
-            out["roofline"]["ceiling"] = {
-                "bound": "per-CU L2 ingest", "bytes_per_cu": nbytes, "workgroups": wgs, "floor_us": floor_us,
-                "frac_of_floor": floor_us / (kernel_ms * 1e3),
-                "frac_if_at_floor": args.batch * fl / (floor_us * 1e-6) / 1e12 / peak,
-                "note": "floor_us = a compute-free read of the same packed weight stream by the same number of workgroups, "
-                        "measured in this run (pf_diag_stream_ingest); frac_of_floor = floor_us / kernel time; "
-                        "frac_if_at_floor = the MFMA-roofline fraction a kernel running AT that floor would show"}
-        if windowed is not None:
-            out["extras"] = {"value_allreduce_every_16": windowed}
-        if not args.no_extras and world == 1:
-            out.setdefault("extras", {}).update(extras(flow, dev, args.batch))
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"], want = cpu_baseline(flow, args.batch)
-            out["parity"] = parity_check(flow, dev, args.batch, want)
-            if args.precision == "bf16" and "extras" in out and f"forward_kernel_us_fp32_{args.batch}" in out["extras"]:
-                # the parity-bearing mode as a first-class block: the reference's arithmetic is fp32 (north_star: 1e-5
-                # relative fp32); the bf16 headline follows the same-rounding oracle, not this tolerance
-                ex, us = out["extras"], out["extras"][f"forward_kernel_us_fp32_{args.batch}"]
-                out["fp32"] = {"samples_per_s": ex[f"forward_samples_per_s_fp32_{args.batch}"], "kernel_ms": us * 1e-3,
-                               "peak_tflops": PEAK_TFLOPS["fp32"], "frac": ex[f"forward_roofline_frac_fp32_{args.batch}"],
-                               "frac_mask_aware": ex[f"forward_roofline_frac_mask_aware_fp32_{args.batch}"],
-                               "dtype": "f32 (v_mfma_f32_16x16x4_f32, fp32 accumulate)", "parity": out["parity"]["fp32"]}
+        if args.full:
+            fl = flops_per_sample()
+            ach = args.batch * fl / (kernel_ms * 1e-3) / 1e12
+            peak = PEAK_TFLOPS[args.precision]
+            # the three FLOP conventions side by side: `achieved` / `frac` use SURVEY 8d's ALGORITHMIC dense-GEMM count (the
+            # contract's figure: masks not discounted); the MFMAs the dispatched kernel really issues multiply the packed
+            # stream, in which all-zero fragments of the autoregressive masks do not exist (pf_flow_issued_flop_per_row), and
+            # the useful share of those is the mask-aware count
+            fl_issued = int(lib.pf_flow_issued_flop_per_row(flow._desc(wide=flow._use_wide(args.batch))))
+            fl_masked = masked_flops_per_sample()
+            tf = lambda f: args.batch * f / (kernel_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
+                               "frac": ach / peak, "traffic": pmc_traffic(args),
+                               "kernel": flow.forward_kernel_name(args.batch), "kernel_ms": kernel_ms,
+                               "flop_convention": "achieved/frac: SURVEY 8d dense-GEMM count (masked zeros counted); *_issued: "
+                                                  "MFMAs the kernel executes (mask-compressed stream); *_mask_aware: useful FLOP only",
+                               "flop_per_sample": fl, "flop_per_sample_issued": fl_issued, "flop_per_sample_mask_aware": fl_masked,
+                               "achieved_issued": tf(fl_issued), "frac_issued": tf(fl_issued) / peak,
+                               "achieved_mask_aware": tf(fl_masked), "frac_mask_aware": tf(fl_masked) / peak,
+                               "device_ms_per_step": dev_ms / args.steps}
+            if world == 1 and args.batch <= 20479:
+                # the bound this design actually has at 16 rows per workgroup: every workgroup ingests the whole packed stream
+                floor_us, nbytes, wgs = ingest_floor_us(flow, args.batch, dev, stream)
+                out["roofline"]["ceiling"] = {
+                    "bound": "per-CU L2 ingest", "bytes_per_cu": nbytes, "workgroups": wgs, "floor_us": floor_us,
+                    "frac_of_floor": floor_us / (kernel_ms * 1e3),
+                    "frac_if_at_floor": args.batch * fl / (floor_us * 1e-6) / 1e12 / peak,
+                    "note": "floor_us = a compute-free read of the same packed weight stream by the same number of workgroups, "
+                            "measured in this run (pf_diag_stream_ingest); frac_of_floor = floor_us / kernel time; "
+                            "frac_if_at_floor = the MFMA-roofline fraction a kernel running AT that floor would show"}
+            if windowed is not None:
+                out["extras"] = {"value_allreduce_every_16": windowed}
+            if not args.no_extras and world == 1:
+                out.setdefault("extras", {}).update(extras(flow, dev, args.batch))
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"], want = cpu_baseline(flow, args.batch)
+                out["parity"] = parity_check(flow, dev, args.batch, want)
+                if args.precision == "bf16" and "extras" in out and f"forward_kernel_us_fp32_{args.batch}" in out["extras"]:
+                    # the parity-bearing mode as a first-class block: the reference's arithmetic is fp32 (north_star: 1e-5
+                    # relative fp32); the bf16 headline follows the same-rounding oracle, not this tolerance
+                    ex, us = out["extras"], out["extras"][f"forward_kernel_us_fp32_{args.batch}"]
+                    out["fp32"] = {"samples_per_s": ex[f"forward_samples_per_s_fp32_{args.batch}"], "kernel_ms": us * 1e-3,
+                                   "peak_tflops": PEAK_TFLOPS["fp32"], "frac": ex[f"forward_roofline_frac_fp32_{args.batch}"],
+                                   "frac_mask_aware": ex[f"forward_roofline_frac_mask_aware_fp32_{args.batch}"],
+                                   "dtype": "f32 (v_mfma_f32_16x16x4_f32, fp32 accumulate)", "parity": out["parity"]["fp32"]}
         print(json.dumps(out))
     if collective:
         dist.destroy_process_group()

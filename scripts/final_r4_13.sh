@@ -4,7 +4,7 @@ set -e
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/r4_13; mkdir -p $OUT; REPO=$PWD
 python -m pytest tests -m gpu -x -q > $OUT/gputests.log 2>&1
-python bench.py > $OUT/bench.log 2>&1
+python bench.py --full > $OUT/bench.log 2>&1
 cd /tmp
 PYTHONPATH=$REPO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/samp -- python3 $REPO/scripts/prof_sampling.py > $OUT/samp.log 2>&1
 cd $REPO

@@ -7,7 +7,7 @@ cd /tmp
 PYTHONPATH=$REPO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/samp -- python3 $REPO/scripts/prof_sampling.py > $OUT/samp.log 2>&1
 cp $(find $OUT/samp -name '*kernel_stats.csv' | head -1) $OUT/sampling_kernel_stats.csv
 rm -rf $OUT/samp
-PYTHONPATH=$REPO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $REPO/bench.py > $OUT/bench.log 2>&1
+PYTHONPATH=$REPO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $REPO/bench.py --full > $OUT/bench.log 2>&1
 cp $(find $OUT/bench -name '*kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv
 rm -rf $OUT/bench
 cd $REPO

@@ -11,10 +11,10 @@ bash $R/scripts/prof_counters_inc.sh inc_r04 > $R/gpurun_out/pmc_inc_r04.log 2>&
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/prof_r4b
 mkdir -p $OUT
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras > $OUT/bench.log 2>&1
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $R/bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-extras > $OUT/bench.log 2>&1
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/sampling -- python3 $R/scripts/prof_sampling.py > $OUT/sampling.log 2>&1
 for P in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 200 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/traffic_$P -- python3 $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/traffic_$P.log 2>&1
+  timeout -k 10 200 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/traffic_$P -- python3 $R/bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-extras > $OUT/traffic_$P.log 2>&1
 done
 cd $R
 for d in bench sampling; do

@@ -15,11 +15,12 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
         "vs_baseline", "dtype", "data", "config", "roofline"}
 
 
-def _run(*flags):
+def _run(*flags, full=True):
+    """one bench.py run; full: with --full, which the roofline block and the windowed all-reduce figure need"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3",
-                          "--no-extras", "--no-cpu-baseline", *flags],
+                          *(("--full", "--no-extras", "--no-cpu-baseline") if full else ()), *flags],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -38,6 +39,27 @@ def test_default_step_contract():
     assert d["value"] > 1e7 and abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
 
 
+def test_plain_run_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the line carries the headline figure and nothing that takes runs of its own; --dump-outputs writes
+    the nll the timed launch left behind, which is the nll of bench.py's seed-1 batch computed here by nll_into."""
+    import numpy as np
+    import torch
+    d = _run("--dump-outputs", str(tmp_path), full=False)
+    assert KEYS - {"roofline"} <= set(d) and not {"roofline", "extras", "cpu_baseline", "parity", "fp32"} & set(d)
+    assert d["steps"] == 20 and d["dtype"] == "bf16" and d["metric"] == "flow.log_prob samples/sec at batch 4096"
+    assert d["value"] > 1e7 and abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert [f.name for f in tmp_path.iterdir()] == ["nll.npy"]
+    got = np.load(tmp_path / "nll.npy")
+    assert got.dtype == np.float32 and got.shape == (4096,) and np.isfinite(got).all()
+    sys.path.insert(0, ROOT)
+    import bench
+    flow = bench.build_flow("cuda:0", "bf16").freeze_packed()
+    x, ctx = bench.make_inputs(4096, 1, "cuda:0")
+    with torch.no_grad():
+        want = flow.nll_into(x, ctx, torch.empty(4096, device="cuda:0")).cpu().numpy()
+    assert np.array_equal(got, want)                         # the same kernel on the same inputs: bit for bit
+
+
 def test_gpus_flag_spawns_the_ranks_itself():
     """`bench.py --gpus 2` with no launcher around it starts two ranks as child processes before touching the GPU
     (gloo rehearsal: both ranks share the one GPU of the box) and reports n_gpus = 2; a --gpus that contradicts
@@ -45,7 +67,7 @@ def test_gpus_flag_spawns_the_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MASTER_PORT="29547")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "12",
-                          "--warmup", "2", "--no-extras", "--no-cpu-baseline"],
+                          "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
