@@ -325,7 +325,8 @@ int64_t pf_flow_inc_layer_bytes(const PfFlowDesc* desc);
  * context_features rounded up to 32 (bf16) / 16 (fp32) and zero columns beyond.  PF_PREC_BF16: context and weights enter the
  * MFMA as bf16 (the forward kernel's operand rounding), fp32 accumulation.  The kernel is the hoisted-projection GEMM of
  * the D-pass inverse (csrc/pf_flow_ctx.hip) with a row-major epilogue; replaces the three context_layer calls nflows makes
- * per MADE pass (reference call site src/ahsd/models/flows.py:637). */
+ * per MADE pass (reference call site src/ahsd/models/flows.py:637).  PF_ERR_UNSUPPORTED, decided on the host, for
+ * context_features > 1024 (fp32) / 2048 (bf16): the width limit of PF_FLAG_HOIST_CTX plans. */
 int pf_flow_ctx_project_rows(int32_t precision, const void* wfrags, const float* bias, const float* ctx, int64_t rows,
                              int32_t context_features, int32_t n_units, float* out, void* stream);
 int pf_flow_inverse_inc(const PfFlowDesc* desc, const int32_t* units_upto_degree, const void* packed,

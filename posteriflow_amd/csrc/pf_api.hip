@@ -61,18 +61,36 @@ int geom_features(const PfGeomArgs& a, hipStream_t st);
 }
 
 namespace {
-thread_local char g_err[256] = "";
+thread_local char g_err[512] = "";
 int fail(int code, const char* msg) {
     std::snprintf(g_err, sizeof(g_err), "%s", msg);
     return code;
 }
+// "<what> (<= 2048 bf16 / 1024 fp32)" with the numbers of pf::ctx_width_limit (pf_layout.h): the one authority
+const char* ctx_limit_msg(const char* what) {
+    static thread_local char msg[160];
+    std::snprintf(msg, sizeof(msg), "%s (<= %d bf16 / %d fp32)", what, pf::ctx_width_limit(true), pf::ctx_width_limit(false));
+    return msg;
+}
 int layout_of(const PfFlowDesc* d, pf::FlowPlan& L) {
     if (!d) return fail(PF_ERR_BAD_ARG, "desc is null");
     const int rc = pf::make_plan(*d, L);
-    if (rc != PF_OK)
-        return fail(rc, "unsupported flow shape (scheduled kernels: D<=H/16, H in {64,128,192,256}, K<=16, num_blocks=2; in-layer "
-                    "context: C<=288, or <=576 in bf16 at H=256 -- wider contexts need PF_FLAG_HOIST_CTX, C<=1024 / 2048 in bf16; "
-                    "generic kernel: plain conditioner, H%16==0, H<=512, D<=32, K<=32, LDS image <= 160 KB)");
+    const bool bf = d->precision == PF_PREC_BF16;
+    if (rc == PF_ERR_UNSUPPORTED && pf::scheduled_shape(*d) && (d->reserved & (PF_FLAG_HOIST_CTX | PF_FLAG_MASKED_CONTEXT)) &&
+        d->context_features > pf::ctx_width_limit(bf)) {
+        // the one width the hoisted projection kernel cannot stage (pf_layout.h kCtxMaxCK): name it
+        std::snprintf(g_err, sizeof(g_err), "context_features = %d exceeds the limit of %d of the %s context-projection kernel "
+                      "(%d k-steps of %d; fp32: %d, bf16: %d)", d->context_features, pf::ctx_width_limit(bf), bf ? "bf16" : "fp32",
+                      pf::kCtxMaxCK, bf ? 32 : 16, pf::ctx_width_limit(false), pf::ctx_width_limit(true));
+        return rc;
+    }
+    if (rc != PF_OK) {
+        std::snprintf(g_err, sizeof(g_err), "unsupported flow shape (scheduled kernels: D<=H/16, H in {64,128,192,256}, K<=16, "
+                      "num_blocks=2; in-layer context: C<=288, or <=576 at H=256 -- wider contexts need PF_FLAG_HOIST_CTX, "
+                      "C<=%d / %d in bf16; generic kernel: plain conditioner, H%%16==0, H<=512, D<=32, K<=32, LDS image <= 160 KB)",
+                      pf::ctx_width_limit(false), pf::ctx_width_limit(true));
+        return rc;
+    }
     if (!(d->tail_bound > 0.f)) return fail(PF_ERR_BAD_ARG, "tail_bound must be positive");
     if (d->min_bin_width * d->num_bins > 1.f || d->min_bin_height * d->num_bins > 1.f)
         return fail(PF_ERR_BAD_ARG, "minimal bin size too large for the number of bins");
@@ -142,7 +160,9 @@ static int project_context(const pf::FlowPlan& L, pf::FwdParams& p, void* worksp
     if (!workspace || workspace_bytes < need) return fail(PF_ERR_BAD_ARG, "workspace too small (pf_flow_workspace_bytes)");
     if (misaligned(workspace, 16)) return fail(PF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
     const int rc = pf::launch_ctx_project(L, p.packed, p.ctx, p.ctx_rows, workspace, s);
-    if (rc != PF_OK) return fail(rc, hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error)));
+    if (rc != PF_OK)
+        return fail(rc, rc == PF_ERR_HIP ? hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error))
+                                         : ctx_limit_msg("context width beyond the projection kernel's LDS tile"));
     p.cproj = workspace;
     return PF_OK;
 }
@@ -676,7 +696,7 @@ int pf_flow_ctx_project_rows(int32_t precision, const void* wfrags, const float*
     if (misaligned(wfrags, 16) || misaligned(bias, 16) || misaligned(out, 16) || misaligned(ctx, 4))
         return fail(PF_ERR_BAD_ARG, "pf_flow_ctx_project_rows: wfrags / bias / out must be 16-byte aligned");
     return finish(pf::ctx_project_rows(precision == PF_PREC_BF16, wfrags, bias, ctx, rows, context_features, n_units, out,
-                                       static_cast<hipStream_t>(stream)), "context width beyond the LDS tile (<= 1280 bf16 / 640 fp32)");
+                                       static_cast<hipStream_t>(stream)), ctx_limit_msg("context width beyond the LDS tile"));
 }
 
 int64_t pf_flow_issued_flop_per_row(const PfFlowDesc* desc) {

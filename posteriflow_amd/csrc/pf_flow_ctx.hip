@@ -35,17 +35,18 @@ struct CtxParams {
     int rowmajor;           // 1: out = raw affine values, fp32 row-major [rows][16 tiles] (the incremental inverse's operand)
 };
 
-constexpr int kCtxRowGroups = 4;   // 64 context rows per workgroup
-
-template <bool BF16>
+// RG 16-row groups per workgroup: 4 (one 64-row block of the output's fragment order per workgroup) while the context tile
+// of CK * RG fragments fits the LDS, 2 (blockIdx.x = (block, half)) for the widest contexts -- pf_layout.h ctx_row_groups
+template <bool BF16, int RG>
 __global__ __launch_bounds__(256) void ctx_project_kernel(const CtxParams p) {
+    constexpr int kCtxRowGroups = RG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4;
     const int64_t row0 = (int64_t)blockIdx.x * 16 * kCtxRowGroups;
 
-    // stage the 64-row context tile: coalesced 16-B global loads of the row-major tile, scattered
+    // stage the 16 RG-row context tile: coalesced 16-B global loads of the row-major tile, scattered
     // into B-fragment order on the LDS side (zero padding beyond C and beyond the last row)
     const int kw = BF16 ? 32 : 16, cpad = p.CK * kw;
     if ((p.C & 3) == 0 && (reinterpret_cast<uintptr_t>(p.ctx) & 15) == 0) {
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void ctx_project_kernel(const CtxParams p) {
         }
     } else {
         for (int s = tid; s < p.CK * kCtxRowGroups * 64; s += 256) {
-            const int ln = s & 63, rg = (s >> 6) & (kCtxRowGroups - 1), ks = s >> 8;
+            const int ln = s & 63, rg = (s >> 6) & (kCtxRowGroups - 1), ks = s / (64 * kCtxRowGroups);
             int64_t row = row0 + 16 * rg + (ln & 15);
             if (row >= p.rows) row = p.rows - 1;
             const float* src = p.ctx + row * p.C;
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(256) void ctx_project_kernel(const CtxParams p) {
             }
             // fragment order [row block of 64][tile][row group][lane][4]: one 1-KiB contiguous
             // store per wave-instruction; rows past the end are padding
-            const size_t off = ((((size_t)blockIdx.x * p.tiles + u) * kCtxRowGroups + rg) * 64 + lane) * 4;
+            const size_t q = (size_t)blockIdx.x * kCtxRowGroups + rg;           // 16-row group of the whole input
+            const size_t off = ((((q >> 2) * p.tiles + u) * 4 + (q & 3)) * 64 + lane) * 4;
             // always fp32: the hoisted path then computes the same function as the in-layer one
             *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + off) = v;
         }
@@ -205,12 +207,25 @@ int ctx_project_rows(bool bf16, const void* wfrags, const float* bias, const flo
     p.frags = reinterpret_cast<const u32x4*>(wfrags);
     p.bias = bias; p.ctx = ctx; p.out = out; p.rows = rows;
     p.C = C; p.CK = (C + kw - 1) / kw; p.NT = 1; p.tiles = n_units / 16; p.additive = 1; p.rowmajor = 1;
-    if ((size_t)p.CK * kCtxRowGroups * kFragBytes > 160 * 1024) return PF_ERR_UNSUPPORTED;
     return launch_ctx(p, bf16, s);
 }
 
+template <bool BF16, int RG>
+static int launch_ctx_rg(const CtxParams& p, unsigned row_blocks, unsigned chunks, hipStream_t s) {
+    auto k = ctx_project_kernel<BF16, RG>;
+    const size_t lds = (size_t)p.CK * RG * kFragBytes;
+    if (lds > 64 * 1024 && !opt_in_lds(reinterpret_cast<const void*>(k), (int)lds)) return PF_ERR_HIP;
+    // whole 64-row blocks also for RG = 2: a half past the last row (loads clamped, row-major stores guarded) is launched
+    // on purpose, it writes the padding of the fragment-ordered output like the 64-row tile does
+    hipLaunchKernelGGL(k, dim3(row_blocks * (4 / RG), chunks), dim3(256), lds, s, p);
+    return launch_status();
+}
+
+// PF_ERR_UNSUPPORTED for a width beyond ctx_width_limit (pf_layout.h): decided here, before any HIP call
 static int launch_ctx(const CtxParams& p_in, bool bf16, hipStream_t s) {
     CtxParams p = p_in;
+    const int rg = ctx_row_groups(p.CK);
+    if (!rg) return PF_ERR_UNSUPPORTED;
     const int64_t ctx_rows = p.rows;
     const unsigned row_blocks = (unsigned)((ctx_rows + 63) / 64);
     // enough workgroups to fill the chip when there are few row blocks
@@ -218,17 +233,8 @@ static int launch_ctx(const CtxParams& p_in, bool bf16, hipStream_t s) {
     while (tpw > 2 && (int64_t)row_blocks * ((p.tiles + 4 * tpw - 1) / (4 * tpw)) < 1024) tpw >>= 1;
     p.tiles_per_wave = tpw;
     const unsigned chunks = (unsigned)((p.tiles + 4 * tpw - 1) / (4 * tpw));
-    const size_t lds = (size_t)p.CK * kCtxRowGroups * kFragBytes;
-    if (bf16) {
-        auto k = ctx_project_kernel<true>;
-        if (lds > 64 * 1024 && !opt_in_lds(reinterpret_cast<const void*>(k), (int)lds)) return PF_ERR_HIP;
-        hipLaunchKernelGGL(k, dim3(row_blocks, chunks), dim3(256), lds, s, p);
-    } else {
-        auto k = ctx_project_kernel<false>;
-        if (lds > 64 * 1024 && !opt_in_lds(reinterpret_cast<const void*>(k), (int)lds)) return PF_ERR_HIP;
-        hipLaunchKernelGGL(k, dim3(row_blocks, chunks), dim3(256), lds, s, p);
-    }
-    return launch_status();
+    if (bf16) return rg == 4 ? launch_ctx_rg<true, 4>(p, row_blocks, chunks, s) : launch_ctx_rg<true, 2>(p, row_blocks, chunks, s);
+    return rg == 4 ? launch_ctx_rg<false, 4>(p, row_blocks, chunks, s) : launch_ctx_rg<false, 2>(p, row_blocks, chunks, s);
 }
 
 }  // namespace pf

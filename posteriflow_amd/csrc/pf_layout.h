@@ -68,6 +68,19 @@ constexpr int kWindowPad = 16;            // frags of zero padding behind each w
 constexpr int kMaxWaves = 8;
 constexpr int kMaxTiles = 16;
 
+// Hoisted-context plans: the projection kernel (pf_flow_ctx.hip) stages its context tile in LDS, CK fragments per 16-row
+// group.  A 64-row tile (4 groups) fits the workgroup's 160 KiB up to CK = 40, a 32-row tile (2 groups) up to kCtxMaxCK;
+// make_plan, the kernel's launcher and pf_flow_ctx_project_rows all take the width limit from here:
+// C <= kCtxMaxCK k-steps = 1024 (fp32, 16 wide) / 2048 (bf16, 32 wide).
+constexpr int kCtxMaxCK = 64;
+constexpr int kCtxLdsBytes = 160 * 1024;
+static_assert(kCtxMaxCK * 2 * kFragBytes <= kCtxLdsBytes, "every width make_plan admits must fit the 2-group tile");
+inline int ctx_row_groups(int CK) {       // 16-row groups per workgroup of the projection kernel; 0: refused
+    if (CK < 1 || CK > kCtxMaxCK) return 0;
+    return (int64_t)CK * 4 * kFragBytes <= kCtxLdsBytes ? 4 : 2;
+}
+inline int ctx_width_limit(bool bf16) { return kCtxMaxCK * (bf16 ? 32 : 16); }
+
 template <bool BF16> constexpr int kPadH = BF16 ? 2 : 5;
 template <bool BF16> constexpr int kPadO = BF16 ? 1 : 2;
 
@@ -221,15 +234,19 @@ inline int make_generic_plan(const PfFlowDesc& d, FlowPlan& o) {
     return PF_OK;
 }
 
+// a shape the scheduled kernels are built for (everything else: the generic kernel's plan)
+inline bool scheduled_shape(const PfFlowDesc& d) {
+    return (d.hidden_features == 64 || d.hidden_features == 128 || d.hidden_features == 192 || d.hidden_features == 256) &&
+           d.features >= 1 && d.features <= d.hidden_features / 16 && d.num_bins >= 2 && d.num_bins <= 16 &&
+           !(d.reserved & PF_FLAG_GENERIC);
+}
+
 // returns 0 on success, PF_ERR_* otherwise
 inline int make_plan(const PfFlowDesc& d, FlowPlan& o) {
     if (d.num_layers < 1 || d.context_features < 0 || d.num_blocks != 2) return PF_ERR_UNSUPPORTED;
     if (d.precision != PF_PREC_F32 && d.precision != PF_PREC_BF16) return PF_ERR_BAD_ARG;
     o.generic = 0;
-    const bool scheduled_shape = (d.hidden_features == 64 || d.hidden_features == 128 || d.hidden_features == 192 ||
-                                  d.hidden_features == 256) &&
-                                 d.features >= 1 && d.features <= d.hidden_features / 16 && d.num_bins >= 2 && d.num_bins <= 16;
-    if (!scheduled_shape || (d.reserved & PF_FLAG_GENERIC)) return make_generic_plan(d, o);
+    if (!scheduled_shape(d)) return make_generic_plan(d, o);
     o.D = d.features; o.C = d.context_features; o.H = d.hidden_features;
     o.K = d.num_bins; o.L = d.num_layers; o.M = 3 * d.num_bins - 1; o.NB = d.num_blocks;
     o.bf16 = d.precision == PF_PREC_BF16;
@@ -252,7 +269,7 @@ inline int make_plan(const PfFlowDesc& d, FlowPlan& o) {
     }
     o.hoist = (d.reserved & (PF_FLAG_HOIST_CTX | PF_FLAG_MASKED_CONTEXT)) && o.C > 0 ? 1 : 0;
     o.CKM = (o.hoist || o.bwd) ? 0 : pick_ckm(o.bf16, o.NT, o.C);      // (the backward stream has no scheduled context slots)
-    if (o.CKM < 0 || o.CK > 64) return PF_ERR_UNSUPPORTED;
+    if (o.CKM < 0 || o.CK > kCtxMaxCK) return PF_ERR_UNSUPPORTED;
     o.HK = o.H / o.kstep;
     int perm[256], deg_sorted[256];
     sorted_units(o.D, o.H, perm);

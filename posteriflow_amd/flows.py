@@ -596,8 +596,10 @@ class NSFPosteriorFlow(nn.Module):
                                           _MIN_BIN, _MIN_BIN, _MIN_BIN, prec, fl)
         desc = make(flags)
         if self.hoist_context is None and not flags and self.context_features > 0:
-            # auto mode: the in-layer context kernels cover C <= 288 (576 in bf16 at H = 256); wider contexts
-            # go through the hoisted projection kernel, which has no such limit
+            # auto mode: the in-layer context kernels cover C <= 288 (576 at H = 256) in either precision;
+            # wider contexts go through the hoisted projection kernel, up to C = 1024 in fp32 / 2048 in bf16
+            # (csrc/pf_layout.h kCtxMaxCK: the one limit make_plan and the projection launchers share).  Beyond it
+            # pf_flow_pack_map_len refuses the plan and packed_weights() raises NotImplementedError naming both
             key = ("inlayer_ok", prec)
             ok = self.__dict__.setdefault("_plan_cache", {}).get(key)
             if ok is None:
@@ -987,19 +989,24 @@ class NSFPosteriorFlow(nn.Module):
                 # (context and weights to bf16, fp32 accumulation) so that forward(inverse(z)) sees the same conditioner
                 cx = context.float().contiguous()
                 proj = torch.empty(cx.shape[0], st["bcat"].numel(), dtype=torch.float32, device=dev)
-                _lib.check(_lib.lib().pf_flow_ctx_project_rows(
+                rc = _lib.lib().pf_flow_ctx_project_rows(
                     _lib.PRECISIONS[self.precision], st["wfrags"].data_ptr(), st["bcat"].data_ptr(), cx.data_ptr(), cx.shape[0],
-                    self.context_features, st["bcat"].numel(), proj.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                    "pf_flow_ctx_project_rows")
-            rc = _lib.lib().pf_flow_inverse_inc(
-                self._desc(self.precision, inverse=True), st["u1"], st["buf"].data_ptr(), _dev_ptr(proj), ctx_rows,
-                z.data_ptr(), _dev_ptr(inv_perm), B, x.data_ptr(), logdet.data_ptr(), flags.data_ptr(),
-                torch.cuda.current_stream(dev).cuda_stream)
-            if rc != _lib.PF_ERR_UNSUPPORTED:
-                _lib.check(rc, "pf_flow_inverse_inc")
-                return x, logdet, flags
-            # more than 8 sixteen-unit tiles of one degree (H / (D - 1) > 112: few features, where the D-pass
-            # kernel needs only 2-3 passes anyway): the D-pass kernel below handles every shape
+                    self.context_features, st["bcat"].numel(), proj.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                if rc != _lib.PF_ERR_UNSUPPORTED:
+                    _lib.check(rc, "pf_flow_ctx_project_rows")
+            else:
+                rc = _lib.PF_OK
+            if rc == _lib.PF_OK:
+                rc = _lib.lib().pf_flow_inverse_inc(
+                    self._desc(self.precision, inverse=True), st["u1"], st["buf"].data_ptr(), _dev_ptr(proj), ctx_rows,
+                    z.data_ptr(), _dev_ptr(inv_perm), B, x.data_ptr(), logdet.data_ptr(), flags.data_ptr(),
+                    torch.cuda.current_stream(dev).cuda_stream)
+                if rc != _lib.PF_ERR_UNSUPPORTED:
+                    _lib.check(rc, "pf_flow_inverse_inc")
+                    return x, logdet, flags
+            # PF_ERR_UNSUPPORTED from either call -- more than 8 sixteen-unit tiles of one degree (H / (D - 1) > 112: few
+            # features, where the D-pass kernel needs only 2-3 passes anyway), or a context the row projection does not
+            # take: the D-pass kernel below serves every shape the plan admits, and refuses the others by name
             self.incremental_inverse = False
         desc = self._desc(inverse=True)
         ws, ws_bytes = self._ws(desc, ctx_rows, dev)

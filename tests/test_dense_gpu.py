@@ -74,9 +74,12 @@ def test_linear_bf16_operands_and_leading_dimensions():
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("rows,c,units", [(1, 288, 8 * 3 * 256), (70, 288, 2 * 3 * 64), (200, 40, 3 * 128)])
+@pytest.mark.parametrize("rows,c,units", [(1, 288, 8 * 3 * 256), (70, 288, 2 * 3 * 64), (200, 40, 3 * 128),
+                                          (70, 641, 3 * 64), (70, 1281, 3 * 64)])
 def test_context_projection_rows_match_tensor_arithmetic(precision, rows, c, units):
-    """pf_flow_ctx_project_rows = the operand of pf_flow_inverse_inc: [rows][units] raw affine values"""
+    """pf_flow_ctx_project_rows = the operand of pf_flow_inverse_inc: [rows][units] raw affine values.  C = 641 (fp32) and
+    1281 (bf16) are one k-step beyond the 64-row context tile: the 32-row variant of the kernel; 1281 in fp32 is beyond
+    the width limit (1024 fp32 / 2048 bf16) and is refused on the host"""
     from posteriflow_amd import _lib
     torch.manual_seed(rows + c)
     dev = torch.device("cuda")
@@ -93,6 +96,12 @@ def test_context_projection_rows_match_tensor_arithmetic(precision, rows, c, uni
     s = torch.cuda.current_stream().cuda_stream
     _lib.check(L.pf_dense_pack_matrix(prec, wp.data_ptr(), 0, kpad, units, kpad, frags.data_ptr(), s), "pack")
     out = torch.full((rows, units), float("nan"), device=dev)
+    if c > (2048 if precision == "bf16" else 1024):
+        rc = L.pf_flow_ctx_project_rows(prec, frags.data_ptr(), b.data_ptr(), ctx.data_ptr(), rows, c, units, out.data_ptr(), s)
+        assert rc == _lib.PF_ERR_UNSUPPORTED and b"1024" in L.pf_last_error()
+        torch.cuda.synchronize()
+        assert torch.isnan(out).all()                       # nothing was launched
+        return
     _lib.check(L.pf_flow_ctx_project_rows(prec, frags.data_ptr(), b.data_ptr(), ctx.data_ptr(), rows, c, units, out.data_ptr(), s), "proj")
     if precision == "bf16":
         ref = ctx.to(torch.bfloat16).double() @ w.to(torch.bfloat16).double().t() + b.double()
