@@ -317,6 +317,14 @@ int pf_flow_inverse(const PfFlowDesc* desc, const void* packed,
  * PF_PREC_F32 (parity mode, v_mfma_f32_16x16x4_f32): the same blocks with fp32 fragments of 16 units x 16 k --
  *   fragment (tile, q), lane (r = lane & 15, kq = lane >> 4): W[16 tile + r][16 q + 4 kq .. + 3] -- , W0 [H][16]
  *   (column f = initial_layer.weight[:, f]); the caller packs them (a reshape / permute, posteriflow_amd/flows.py).
+ * Wide heads (csrc/pf_flow_inc_wide.hip) -- H > 256 or K > 16 are served by a second kernel, 16 draws per 8-wave workgroup,
+ *   one workgroup per CU: H a multiple of 32 up to 512, 2 <= K <= 32, 2 <= D <= min(16, H / 16), two residual blocks,
+ *   context or none; PF_PREC_BF16 for every such H, PF_PREC_F32 for H <= 384 only (five fp32 stages of 16 rows x 512 units
+ *   would be the whole 160 KB of LDS).  The layer block has the same sections in the same order; for K > 16 the final layer
+ *   is [D * 96][H] -- per feature 32 width rows, 32 height rows, 32 derivative rows, zero padded -- and the final bias
+ *   [D][96].  pf_flow_inc_layer_bytes = (H/16 + 4 (H/16) HK + T D HK) * 1024 + (5 H + 16 T D) * 4 with HK = H / 32 (bf16) or
+ *   H / 16 (fp32) fragments per tile row and T = 3 (K <= 16) or 6 tail tiles per feature; -1 outside the two kernels' domain.
+ *   PF_ERR_UNSUPPORTED (use pf_flow_inverse): fp32 at H > 384, D > 16, more than 8 new sixteen-unit tiles in one pass.
  * z, x, logdet, fail_flags, ar_inv_perm, ctx_rows as in pf_flow_inverse. */
 int pf_pack_bf16_frags(const float* src, int32_t n_rows, int32_t k, void* out, void* stream);
 int64_t pf_flow_inc_layer_bytes(const PfFlowDesc* desc);

@@ -23,6 +23,10 @@ int fusion_forward(const char* packed, float* tokens, int n_tokens, const float*
                    int64_t n_events, float* pooled, hipStream_t s);
 int inc_pack_frags(const float* src, int n_rows, int k, void* out, hipStream_t s);
 int64_t inc_layer_bytes(int D, int H, bool f32);
+int64_t inc_wide_layer_bytes(int D, int H, int K, bool f32);
+int flow_inverse_inc_wide(const PfFlowDesc& d, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
+                          int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x, float* logdet,
+                          uint32_t* fail, hipStream_t s);
 int flow_inverse_inc(const PfFlowDesc& d, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
                      int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x, float* logdet,
                      uint32_t* fail, hipStream_t s);
@@ -432,18 +436,26 @@ int pf_pack_bf16_frags(const float* src, int32_t n_rows, int32_t k, void* out, v
     const int rc = pf::inc_pack_frags(src, n_rows, k, out, static_cast<hipStream_t>(stream));
     return rc == PF_OK ? rc : fail(rc, hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error)));
 }
+// the wide kernel (pf_flow_inc_wide.hip) serves what the first one refuses: H > 256 or K > 16
+static bool inc_wide_shape(const PfFlowDesc* d) { return d->hidden_features > 256 || d->num_bins > 16; }
 int64_t pf_flow_inc_layer_bytes(const PfFlowDesc* desc) {
-    if (!desc || desc->hidden_features % 32 || desc->hidden_features < 64 || desc->hidden_features > 256) return -1;
-    return pf::inc_layer_bytes(desc->features, desc->hidden_features, desc->precision == PF_PREC_F32);
+    if (!desc || desc->hidden_features % 32 || desc->hidden_features < 64) return -1;
+    const bool f32 = desc->precision == PF_PREC_F32;
+    if (!inc_wide_shape(desc)) return pf::inc_layer_bytes(desc->features, desc->hidden_features, f32);
+    if (desc->hidden_features > (f32 ? 384 : 512) || desc->num_bins > 32 || desc->features < 2 || desc->features > 16) return -1;
+    return pf::inc_wide_layer_bytes(desc->features, desc->hidden_features, desc->num_bins, f32);
 }
 int pf_flow_inverse_inc(const PfFlowDesc* desc, const int32_t* units_upto_degree, const void* packed,
                         const float* ctx_proj, int64_t ctx_rows, const float* z, const int32_t* ar_inv_perm,
                         int64_t batch, float* x, float* logdet, uint32_t* fail_flags, void* stream) {
     if (!desc) return fail(PF_ERR_BAD_ARG, "desc is null");
     const int D = desc->features, H = desc->hidden_features;
-    if (H % 32 || H < 64 || H > 256 || D < 1 || D > 16 || D > H / 16 || desc->num_bins < 2 || desc->num_bins > 16 ||
+    const bool wide = inc_wide_shape(desc);
+    if (H % 32 || H < 64 || H > 512 || D < (wide ? 2 : 1) || D > 16 || D > H / 16 || desc->num_bins < 2 || desc->num_bins > 32 ||
         desc->num_blocks != 2)
-        return fail(PF_ERR_UNSUPPORTED, "incremental inverse: need H in 64..256 (multiple of 32), D <= min(16, H/16), K <= 16");
+        return fail(PF_ERR_UNSUPPORTED, "incremental inverse: need H in 64..512 (multiple of 32), D <= min(16, H/16), K <= 32");
+    if (wide && desc->precision == PF_PREC_F32 && H > 384)
+        return fail(PF_ERR_UNSUPPORTED, "incremental inverse: fp32 needs H <= 384 (five fp32 stages of 16 rows x 512 units are the whole LDS)");
     if (!(desc->tail_bound > 0.f)) return fail(PF_ERR_BAD_ARG, "tail_bound must be positive");
     if (batch < 0) return fail(PF_ERR_BAD_ARG, "negative batch");
     if (batch == 0) return PF_OK;
@@ -454,8 +466,9 @@ int pf_flow_inverse_inc(const PfFlowDesc* desc, const int32_t* units_upto_degree
     for (int i = 0; i < D; ++i)
         if (units_upto_degree[i] > units_upto_degree[i + 1]) return fail(PF_ERR_BAD_ARG, "units_upto_degree must be non-decreasing");
     const float dc = (float)std::log(std::exp(1.0 - (double)desc->min_derivative) - 1.0);
-    const int rc = pf::flow_inverse_inc(*desc, dc, units_upto_degree, packed, ctx_proj, ctx_proj ? ctx_rows : batch, z,
-                                        ar_inv_perm, batch, x, logdet, fail_flags, static_cast<hipStream_t>(stream));
+    const int rc = (wide ? pf::flow_inverse_inc_wide : pf::flow_inverse_inc)(
+        *desc, dc, units_upto_degree, packed, ctx_proj, ctx_proj ? ctx_rows : batch, z, ar_inv_perm, batch, x, logdet, fail_flags,
+        static_cast<hipStream_t>(stream));
     if (rc == PF_ERR_UNSUPPORTED) return fail(rc, "incremental inverse: more than 8 sixteen-unit tiles hold the units of one degree");
     return rc == PF_OK ? rc : fail(rc, hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error)));
 }

@@ -878,15 +878,22 @@ class NSFPosteriorFlow(nn.Module):
 
     def _generic_shape(self) -> bool:
         """a shape outside the scheduled kernels' set (e.g. the 12 x 384 x 24 head of experiments/frozen_context_heads.py:
-        159-163): evaluated by the generic kernel (csrc/pf_flow_generic.hip) -- forward and the D-pass inverse, no gradients"""
+        159-163): evaluated by the generic kernel (csrc/pf_flow_generic.hip) -- forward and the D-pass inverse, no gradients;
+        sampling of the wide ones among them goes through the incremental inverse, see _use_incremental"""
         return not (self.hidden_features in (64, 128, 192, 256) and 1 <= self.features <= self.hidden_features // 16
                     and 2 <= self.num_bins <= 16)
 
     def _use_incremental(self) -> bool:
-        if self.incremental_inverse is False or self.use_masked_context or self._generic_shape():
+        if self.incremental_inverse is False or self.use_masked_context:
+            return False
+        # scheduled shapes: csrc/pf_flow_inc.hip; H above 256 (up to 512) or K above 16 (up to 32): csrc/pf_flow_inc_wide.hip
+        # (what that kernel refuses inside this range -- fp32 above H = 384, more than 8 new tiles in a pass -- comes back as
+        # PF_ERR_UNSUPPORTED); the other generic shapes stay on the D-pass kernel
+        if self._generic_shape() and not (self.hidden_features > 256 or self.num_bins > 16):
             return False
         # features == 1: every hidden unit has degree 0 (one pass, nothing incremental about it): D-pass kernel
-        return (self.hidden_features % 32 == 0 and 2 <= self.features <= min(16, self.hidden_features // 16))
+        return (self.hidden_features % 32 == 0 and 64 <= self.hidden_features <= 512 and 2 <= self.num_bins <= 32
+                and 2 <= self.features <= min(16, self.hidden_features // 16))
 
     def _inc_state(self, dev):
         """Weights of every layer in the layout of pf_flow_inverse_inc (hidden units sorted by degree, masks
@@ -905,8 +912,8 @@ class NSFPosteriorFlow(nn.Module):
         deg_sorted = deg[perm]
         u1 = (_lib.C.c_int32 * (D + 1))(*[int((deg_sorted <= i).sum()) for i in range(D + 1)])
         layer_bytes = L_.pf_flow_inc_layer_bytes(desc)
-        if layer_bytes <= 0:
-            _lib.check(_lib.PF_ERR_UNSUPPORTED, "pf_flow_inc_layer_bytes")
+        if layer_bytes <= 0:                 # outside the incremental kernels' domain (e.g. fp32 at H = 512): the caller falls back
+            return None
         nl = self.num_layers
         buf = torch.empty(nl * layer_bytes, dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -940,16 +947,19 @@ class NSFPosteriorFlow(nn.Module):
                         off = pack((lin.weight * lin.mask)[perm][:, perm], off)
                         biases.append(lin.bias[perm])
                 wf = (net.final_layer.weight * net.final_layer.mask)[:, perm].reshape(D, 3 * K - 1, H)
-                wf48 = torch.zeros(D, 48, H, device=dev)
+                # per feature: KP width rows | KP height rows | KP derivative rows, zero padded (KP = 16, or 32 when K > 16:
+                # the wide kernel's six tail tiles)
+                KP = 16 if K <= 16 else 32
+                wf48 = torch.zeros(D, 3 * KP, H, device=dev)
                 wf48[:, 0:K] = wf[:, 0:K]
-                wf48[:, 16:16 + K] = wf[:, K:2 * K]
-                wf48[:, 32:32 + K - 1] = wf[:, 2 * K:]
-                off = pack(wf48.reshape(D * 48, H), off)
+                wf48[:, KP:KP + K] = wf[:, K:2 * K]
+                wf48[:, 2 * KP:2 * KP + K - 1] = wf[:, 2 * K:]
+                off = pack(wf48.reshape(D * 3 * KP, H), off)
                 bf = net.final_layer.bias.reshape(D, 3 * K - 1)
-                bf48 = torch.zeros(D, 48, device=dev)
+                bf48 = torch.zeros(D, 3 * KP, device=dev)
                 bf48[:, 0:K] = bf[:, 0:K]
-                bf48[:, 16:16 + K] = bf[:, K:2 * K]
-                bf48[:, 32:32 + K - 1] = bf[:, 2 * K:]
+                bf48[:, KP:KP + K] = bf[:, K:2 * K]
+                bf48[:, 2 * KP:2 * KP + K - 1] = bf[:, 2 * K:]
                 vec = torch.cat([b.float() for b in biases] + [bf48.reshape(-1)]).contiguous()
                 assert off + vec.numel() * 4 == (l + 1) * layer_bytes
                 buf[off:off + vec.numel() * 4].copy_(vec.view(torch.uint8))
@@ -982,8 +992,10 @@ class NSFPosteriorFlow(nn.Module):
         _, inv_perm = self._perms(dev)
         if self._use_incremental():
             st = self._inc_state(dev)
-            proj = None
-            if st["wfrags"] is not None:
+            proj, rc = None, _lib.PF_OK
+            if st is None:                   # no layer block for this shape: as refused as by the kernel itself
+                rc = _lib.PF_ERR_UNSUPPORTED
+            elif st["wfrags"] is not None:
                 # [ctx_rows, L * 3 * H]: one GEMM for every layer's three context projections (pf_flow_ctx_project_rows: the
                 # hoisted-projection kernel with a row-major epilogue), with the operand rounding of the bf16 forward kernel
                 # (context and weights to bf16, fp32 accumulation) so that forward(inverse(z)) sees the same conditioner
@@ -994,8 +1006,6 @@ class NSFPosteriorFlow(nn.Module):
                     self.context_features, st["bcat"].numel(), proj.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
                 if rc != _lib.PF_ERR_UNSUPPORTED:
                     _lib.check(rc, "pf_flow_ctx_project_rows")
-            else:
-                rc = _lib.PF_OK
             if rc == _lib.PF_OK:
                 rc = _lib.lib().pf_flow_inverse_inc(
                     self._desc(self.precision, inverse=True), st["u1"], st["buf"].data_ptr(), _dev_ptr(proj), ctx_rows,
@@ -1005,8 +1015,8 @@ class NSFPosteriorFlow(nn.Module):
                     _lib.check(rc, "pf_flow_inverse_inc")
                     return x, logdet, flags
             # PF_ERR_UNSUPPORTED from either call -- more than 8 sixteen-unit tiles of one degree (H / (D - 1) > 112: few
-            # features, where the D-pass kernel needs only 2-3 passes anyway), or a context the row projection does not
-            # take: the D-pass kernel below serves every shape the plan admits, and refuses the others by name
+            # features, where the D-pass kernel needs only 2-3 passes anyway), fp32 above H = 384, or a context the row
+            # projection does not take: the D-pass kernel below serves every shape the plan admits, and refuses the others by name
             self.incremental_inverse = False
         desc = self._desc(inverse=True)
         ws, ws_bytes = self._ws(desc, ctx_rows, dev)

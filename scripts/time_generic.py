@@ -1,4 +1,6 @@
-"""Throughput of the generic-shape kernel on FlowHead(12, 384, 24) of experiments/frozen_context_heads.py:159-163."""
+"""Throughput of the generic-shape kernels on FlowHead(12, 384, 24) of experiments/frozen_context_heads.py:159-163:
+forward, and the inverse on the incremental kernel (csrc/pf_flow_inc_wide.hip, the default) against the D-pass kernel
+(incremental_inverse = False) at 4096 and 131 072 draws with one context row -- median of repeated timed launches."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from posteriflow_amd import NSFPosteriorFlow
@@ -12,11 +14,28 @@ def t(fn, n=10):
     fn(); torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(n): fn()
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / n * 1e3
+def median_ms(fn, warm=3, n=15):
+    for _ in range(warm): fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record(); b.synchronize()
+        out.append(a.elapsed_time(b))
+    return sorted(out)[n // 2]
 for prec in ("fp32", "bf16"):
     flow.precision = prec
     ms = t(lambda: flow.compute_psd_aware_nll(x, ctx, None))
     flop = 2 * 12 * (11 * 384 + 288 * 384 + 2 * (2 * 384 * 384 + 288 * 384) + 384 * 11 * 71)
-    z = torch.randn(B, 11, device="cuda")
-    mi = t(lambda: flow.inverse(z, ctx[:1].expand(B, -1)), n=3)
-    print(f"{prec}: forward {ms:.3f} ms per {B} rows = {B / ms / 1e3:.2f} M samples/s = {B * flop / ms / 1e9:.1f} TFLOP/s (dense count); "
-          f"inverse {mi:.2f} ms per {B} draws = {B / mi / 1e3:.3f} M draws/s")
+    print(f"{prec}: forward {ms:.3f} ms per {B} rows = {B / ms / 1e3:.2f} M samples/s = {B * flop / ms / 1e9:.1f} TFLOP/s (dense count)")
+    for draws in (4096, 131072):
+        z = torch.randn(draws, 11, device="cuda")
+        res = {}
+        for inc in (None, False):
+            flow.incremental_inverse = inc
+            res[inc] = median_ms(lambda: flow.inverse(z, ctx[:1]), n=15 if draws == 4096 else 5)
+            served = "incremental" if flow.incremental_inverse is None else "d-pass"
+            print(f"{prec}: inverse of {draws} draws, one context row, {served} kernel: {res[inc]:.3f} ms = "
+                  f"{draws / res[inc] / 1e3:.3f} M draws/s")
+        flow.incremental_inverse = None
+        print(f"{prec}: {draws} draws: incremental / d-pass = {res[False] / res[None]:.2f}x")
