@@ -105,7 +105,8 @@ typedef struct PfFlowDesc {
  * hidden_features % 16 == 0, <= 512, features <= 32, num_bins <= 32 whose workgroup image fits 160 KB of LDS (the reference
  * also builds 12 x 384 x 24 heads, experiments/frozen_context_heads.py:159-163) is served by one generic kernel behind the
  * SAME entry points: pf_flow_raw_param_count / packed_bytes / pack_map_len / build_pack_map / pack, pf_flow_forward,
- * pf_flow_forward_reduce, pf_flow_forward_train (layer inputs; no dropout), pf_flow_inverse, and -- fp32 descs, features <= 16,
+ * pf_flow_forward_reduce, pf_flow_forward_train (layer inputs), pf_flow_forward_train_dropout / pf_flow_dropout_mask (the
+ * plan of the flow's own desc, not the PF_FLAG_GENERIC layout), pf_flow_inverse, and -- fp32 descs, features <= 16,
  * hidden_features in {64, 128, 192, 256, 384, 512}, num_bins <= 32 -- pf_flow_reevaluate (PF_FLAG_GENERIC layout),
  * pf_flow_backward_chain and pf_flow_rqs_backward.  The incremental-inverse, large-batch and bf16 backward entry points return
  * PF_ERR_UNSUPPORTED for such a shape.
@@ -170,7 +171,10 @@ int pf_flow_forward_train(const PfFlowDesc* desc, const void* packed,
  * MaskedResidualBlock applies dropout after the second activation of every residual block.  The keep decision of
  * (row, layer, block, hidden unit) is a counter hash of dropout_seed -- kept values are scaled by 1 / (1 - p) -- so the
  * backward regenerates the factors with pf_flow_dropout_mask: mask[2][L][batch][H] (block, layer, row, unit in nflows
- * order), each 0 or 1 / (1 - p).  dropout_p = 0 is pf_flow_forward_train.  Not available with PF_FLAG_WIDE. */
+ * order), each 0 or 1 / (1 - p).  dropout_p = 0 is pf_flow_forward_train.  Not available with PF_FLAG_WIDE.
+ * The counter of a decision is (2 layer + block) * stride + pos + 1, pos = the rank of the hidden unit in the stable sort by
+ * MADE degree, stride = 256 for hidden_features <= 256 and 512 above (generic shapes up to 512 units: every block keeps its own
+ * counter range).  Both calls serve scheduled and generic shapes alike, in both precisions. */
 int pf_flow_forward_train_dropout(const PfFlowDesc* desc, const void* packed,
                                   const float* x, const float* ctx, const int32_t* ar_perm,
                                   const float* log_sigma, int64_t batch,

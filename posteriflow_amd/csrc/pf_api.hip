@@ -221,13 +221,12 @@ int pf_flow_dropout_mask(const PfFlowDesc* desc, float dropout_p, uint64_t dropo
     pf::FlowPlan L;
     int rc = layout_of(desc, L);
     if (rc != PF_OK) return rc;
-    if (L.generic) return fail(PF_ERR_UNSUPPORTED, "the generic-shape kernel is an evaluation kernel: no dropout");
     if (batch < 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return fail(PF_ERR_BAD_ARG, "need batch >= 0 and dropout_p in [0, 1)");
     if (batch == 0) return PF_OK;
     if (!mask) return fail(PF_ERR_BAD_ARG, "mask is null");
     rc = pf::launch_dropout_mask(L, drop_threshold(dropout_p), static_cast<uint32_t>(dropout_seed ^ (dropout_seed >> 32)),
                                  1.f / (1.f - dropout_p), batch, mask, static_cast<hipStream_t>(stream));
-    return rc == PF_OK ? rc : fail(rc, rc == PF_ERR_HIP ? hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error)) : "hidden_features > 256");
+    return rc == PF_OK ? rc : fail(rc, rc == PF_ERR_HIP ? hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error)) : "hidden_features > 512");
 }
 int pf_flow_forward_reduce(const PfFlowDesc* desc, const void* packed, const float* x, const float* ctx,
                            const int32_t* ar_perm, const float* log_sigma, int64_t batch, float* nll,

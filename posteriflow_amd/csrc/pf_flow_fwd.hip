@@ -80,7 +80,7 @@ int rows_per_workgroup(const FlowPlan& L, int64_t batch) { return rows_per_workg
 // the kernel launch_flow_forward picks for (plan, batch), as rocprofv3 prints it
 void forward_kernel_name(const FlowPlan& L, int64_t batch, char* out, size_t n) {
     if (L.wide) { snprintf(out, n, use_mid(L, batch) ? "pf::flow_mid_kernel<%d, %d>" : "pf::flow_wide_kernel<%d, %d>", L.D, L.CKM); return; }
-    if (L.generic) { snprintf(out, n, "pf::flow_generic_kernel<%s, false>", L.bf16 ? "true" : "false"); return; }
+    if (L.generic) { snprintf(out, n, "pf::flow_generic_kernel<%s, 0, false>", L.bf16 ? "true" : "false"); return; }
     const int R = L.dense == 1 ? 1 : rows_per_workgroup(L, batch) / 16;
     snprintf(out, n, "pf::flow_kernel<%s, %d, %d, %d, %d, false>", L.bf16 ? "true" : "false", L.NT, R, L.CKM, L.dense);
 }
@@ -89,7 +89,12 @@ int launch_flow_generic(const FwdParams& p, bool inverse, hipStream_t s);       
 
 int launch_flow_forward(const FwdParams& p_in, hipStream_t s) {
     if (p_in.batch == 0) return PF_OK;
-    if (p_in.plan.generic) return p_in.drop_thresh ? (int)PF_ERR_UNSUPPORTED : launch_flow_generic(p_in, false, s);
+    if (p_in.plan.generic) {
+        // dropout hashes the degree-sorted position = the LDS position of a sorted plan (D = 1: one degree, nflows order is sorted);
+        // the PF_FLAG_GENERIC layout keeps nflows order and is the re-evaluation's, which reads the factors from memory
+        if (p_in.drop_thresh && !p_in.plan.gsorted && p_in.plan.D > 1) return PF_ERR_UNSUPPORTED;
+        return launch_flow_generic(p_in, false, s);
+    }
     if (p_in.plan.wide) {
         if (p_in.drop_thresh) return PF_ERR_UNSUPPORTED;   // the large-batch kernels are evaluation kernels
         if (use_mid(p_in.plan, p_in.batch)) {
@@ -115,16 +120,18 @@ int launch_flow_forward(const FwdParams& p_in, hipStream_t s) {
     return PF_ERR_UNSUPPORTED;
 }
 
-// The dropout factors flow_train_kernel applied, for the backward: mask[j][l][row][unit] in {0, 1 / (1 - p)}, units in
-// nflows order (the kernel hashes the degree-sorted position; sorted_units maps it back).
+// The dropout factors the training forward applied (flow_train_kernel; generic plans: flow_generic_kernel<.., 0, true>), for
+// the backward: mask[j][l][row][unit] in {0, 1 / (1 - p)}, units in nflows order (the kernels hash the degree-sorted position --
+// the order of the scheduled tiles and of a generic plan's sorted layout alike; sorted_units maps it back).
 namespace {
+constexpr int kDropMaxH = 512;
 struct DropMaskArgs {
     float* mask;
     int64_t batch;
     int L, H;
-    uint32_t thresh, seed;
+    uint32_t thresh, seed, stride;
     float scale;
-    uint8_t pos_of_unit[256];
+    uint16_t pos_of_unit[kDropMaxH];
 };
 __global__ __launch_bounds__(256) void dropout_mask_kernel(const DropMaskArgs a) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, n = 2 * (int64_t)a.L * a.batch * a.H;
@@ -132,16 +139,16 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(const DropMaskArgs a)
     const int u = (int)(idx % a.H);
     const int64_t t = idx / a.H, row = t % a.batch, jl = t / a.batch;
     const int l = (int)(jl % a.L), j = (int)(jl / a.L);
-    a.mask[idx] = drop_factor(drop_row_hash(a.seed, (uint32_t)row), 2 * l + j, a.pos_of_unit[u], a.thresh, a.scale);
+    a.mask[idx] = drop_factor(drop_row_hash(a.seed, (uint32_t)row), 2 * l + j, a.pos_of_unit[u], a.stride, a.thresh, a.scale);
 }
 }  // namespace
 
 int launch_dropout_mask(const FlowPlan& L, uint32_t thresh, uint32_t seed, float scale, int64_t batch, float* mask, hipStream_t s) {
-    if (L.H > 256) return PF_ERR_UNSUPPORTED;
-    DropMaskArgs a{mask, batch, L.L, L.H, thresh, seed, scale, {}};
-    int perm[256];
+    if (L.H < 1 || L.H > kDropMaxH) return PF_ERR_UNSUPPORTED;
+    DropMaskArgs a{mask, batch, L.L, L.H, thresh, seed, drop_stride(L.H), scale, {}};
+    int perm[kDropMaxH];
     sorted_units(L.D, L.H, perm);
-    for (int p = 0; p < L.H; ++p) a.pos_of_unit[perm[p]] = (uint8_t)p;
+    for (int p = 0; p < L.H; ++p) a.pos_of_unit[perm[p]] = (uint16_t)p;
     const int64_t n = 2 * (int64_t)L.L * batch * L.H;
     if (n == 0) return PF_OK;
     dropout_mask_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(a);

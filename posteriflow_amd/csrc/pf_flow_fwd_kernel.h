@@ -733,8 +733,8 @@ __device__ __forceinline__ void flow_body(const FwdParams& p) {
                         const uint32_t hr = drop_row_hash(p.drop_seed, (uint32_t)(row0 + 16 * r + c));
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            tAv[r][e] *= drop_factor(hr, 2 * l + b, 16 * tA + 4 * g + e, p.drop_thresh, p.drop_scale);
-                            tBv[r][e] *= drop_factor(hr, 2 * l + b, 16 * tB + 4 * g + e, p.drop_thresh, p.drop_scale);
+                            tAv[r][e] *= drop_factor(hr, 2 * l + b, 16 * tA + 4 * g + e, drop_stride(16 * NT), p.drop_thresh, p.drop_scale);
+                            tBv[r][e] *= drop_factor(hr, 2 * l + b, 16 * tB + 4 * g + e, drop_stride(16 * NT), p.drop_thresh, p.drop_scale);
                         }
                     }
                 }

@@ -98,8 +98,18 @@ struct ReevalSink {
 };
 
 // MODE 0: forward, 1: D-pass inverse, 2: one layer's conditioner per workgroup (grid.y = layer), everything written out
-template <bool BF16, int MODE>
+// DROP (MODE 0 only): the training forward of a flow with conditioner dropout.  nflows' MaskedResidualBlock (and the reference's
+// masked-context block, flows.py:225-234) drops after the second activation: relu(W1 relu(h) + b1 [+ Wg ctx + bg]) is multiplied
+// by the factor of (row, layer-block, sorted position) before the block's second masked linear.  Here that is the epilogue of the
+// first linear: its accumulator tile gets bias, ReLU and the conversion to the second linear's B rows in LDS, and the factor goes
+// in between, in fp32.  A lane's four accumulator elements are four consecutive positions 16 t + 4 g + e of ONE row row0 + c, so
+// the row half of the counter hash (drop_row_hash) is computed once per lane and launch and the per-unit half (drop_hash) is
+// a dozen VALU instructions per element next to the tile's k-steps of MFMA; no LDS, no memory traffic, no stored mask
+// (pf_flow_dropout_mask regenerates the factors for the backward).  The position is the LDS position of a SORTED plan
+// (launch_flow_forward refuses the nflows-order layout), the counter stride drop_stride(H).
+template <bool BF16, int MODE, bool DROP = false>
 __global__ __launch_bounds__(kGenWaves * 64) void flow_generic_kernel(const FwdParams p, const ReevalSink sink) {
+    static_assert(!DROP || MODE == 0, "dropout belongs to the training forward");
     constexpr bool INV = MODE == 1, REEVAL = MODE == 2;
     constexpr bool FAST = BF16;
     constexpr int KSTEP = BF16 ? 32 : 16, ESZ = BF16 ? 2 : 4;
@@ -112,6 +122,13 @@ __global__ __launch_bounds__(kGenWaves * 64) void flow_generic_kernel(const FwdP
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, c = lane & 15;
     const int64_t row0 = (int64_t)blockIdx.x * 16;
+    // DROP: the lane's row.  Rows at or beyond batch (ragged last workgroup) repeat the last row -- as their x and context do --
+    // and nothing of them is stored
+    uint32_t drop_row = 0, drop_str = 0;
+    if constexpr (DROP) {
+        drop_row = drop_row_hash(p.drop_seed, (uint32_t)(row0 + c < p.batch ? row0 + c : p.batch - 1));
+        drop_str = drop_stride(H);
+    }
 
     // ---- LDS carve: operand rows (act type, 16-byte pad per row), residual, spline parameters, small fp32 vectors --------
     const int sx = L.gKx * KSTEP * ESZ + 16, sc = L.gKc * KSTEP * ESZ + 16, sh = L.gKh * KSTEP * ESZ + 16;
@@ -279,9 +296,23 @@ __global__ __launch_bounds__(kGenWaves * 64) void flow_generic_kernel(const FwdP
             for (int t = wave; t < NT; t += kGenWaves) {                           // t1 = W1 relu(h) + b1; s_b = relu(t1)
                 const int kh = kmax_hidden(t);
                 f32x4 v = mm(f1, t, L.gKh, kh, s_a, sh) + *reinterpret_cast<const f32x4*>(b_blk + (2 * b) * H + 16 * t + 4 * g);
-                if (additive)          // t1 = W1 relu(h) + b1 + context_layer(ctx)   (flows.py:225-234)
-                    v = v + mm(b == 0 ? f_g0 : f_g1, t, L.gKc, L.gKc, s_ctx, sc) + *reinterpret_cast<const f32x4*>((b == 0 ? b_g0 : b_g1) + 16 * t + 4 * g);
+                if (additive) {        // t1 = W1 relu(h) + b1 + context_layer(ctx)   (flows.py:225-234)
+                    const f32x4 cv = mm(b == 0 ? f_g0 : f_g1, t, L.gKc, L.gKc, s_ctx, sc);
+                    if constexpr (DROP && !BF16) {
+                        // the fp32 DROP instantiation adds into this product's registers 9 wait states behind the last MFMA of
+                        // mm's tail loop, across the loop's exit branch; scripts/audit_accvgpr.py asks for the 10 of an 8-pass
+                        // f32 MFMA (as in pf_flow_inc_wide.hip): two explicit states the compiler's own count does not see
+                        __builtin_amdgcn_sched_barrier(0);
+                        asm volatile("s_nop 1");
+                    }
+                    v = v + cv + *reinterpret_cast<const f32x4*>((b == 0 ? b_g0 : b_g1) + 16 * t + 4 * g);
+                }
                 f32x4 df = {1.f, 1.f, 1.f, 1.f};
+                if constexpr (DROP) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        df[e] = drop_factor(drop_row, (uint32_t)(2 * l + b), (uint32_t)(16 * t + 4 * g + e), drop_str, p.drop_thresh, p.drop_scale);
+                }
                 if constexpr (REEVAL) {
                     if (row0 + c < p.batch) {
                         const size_t o = (((size_t)b * L.L + l) * p.batch + row0 + c) * H + 16 * t + 4 * g;
@@ -422,10 +453,10 @@ __global__ __launch_bounds__(kGenWaves * 64) void flow_generic_kernel(const FwdP
     }
 }
 
-template <bool BF16, int MODE>
+template <bool BF16, int MODE, bool DROP = false>
 int launch_generic_t(const FwdParams& p, const ReevalSink& sink, hipStream_t s) {
     const size_t lds = (size_t)p.plan.gen_lds_bytes();
-    auto k = flow_generic_kernel<BF16, MODE>;
+    auto k = flow_generic_kernel<BF16, MODE, DROP>;
     if (lds > 160 * 1024) return PF_ERR_UNSUPPORTED;
     if (lds > 64 * 1024 && !opt_in_lds(reinterpret_cast<const void*>(k), (int)lds)) return PF_ERR_HIP;
     const unsigned grid = (unsigned)((p.batch + 15) / 16);
@@ -438,6 +469,10 @@ int launch_generic_t(const FwdParams& p, const ReevalSink& sink, hipStream_t s) 
 
 int launch_flow_generic(const FwdParams& p, bool inverse, hipStream_t s) {
     const ReevalSink none{};
+    if (p.drop_thresh) {          // training forward with dropout (pf_flow_forward_train_dropout); the inverse has none
+        if (inverse) return PF_ERR_UNSUPPORTED;
+        return p.plan.bf16 ? launch_generic_t<true, 0, true>(p, none, s) : launch_generic_t<false, 0, true>(p, none, s);
+    }
     if (p.plan.bf16) return inverse ? launch_generic_t<true, 1>(p, none, s) : launch_generic_t<true, 0>(p, none, s);
     return inverse ? launch_generic_t<false, 1>(p, none, s) : launch_generic_t<false, 0>(p, none, s);
 }

@@ -34,19 +34,22 @@ struct FwdParams {
 };
 
 // Dropout decision of (row, layer-block lb = 2 l + b, degree-sorted position pos): a counter hash, so that the forward kernel
-// and the mask kernel the backward uses (pf_flow_dropout_mask) agree without a stored mask.
+// and the mask kernel the backward uses (pf_flow_dropout_mask) agree without a stored mask.  The counter of a decision is
+// lb * stride + pos + 1 with stride = drop_stride(H): 256 up to H = 256 (the scheduled kernels' values, pinned by the tests),
+// 512 above -- with 256 position 256 + i of a block would take the counter of position i of the next one.
+__host__ __device__ constexpr uint32_t drop_stride(int H) { return H > 256 ? 512u : 256u; }
 __host__ __device__ inline uint32_t drop_row_hash(uint32_t seed, uint32_t row) {
     uint32_t x = seed ^ (row * 0x9E3779B1u);
     x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
     return x;
 }
-__host__ __device__ inline uint32_t drop_hash(uint32_t row_hash, uint32_t lb, uint32_t pos) {
-    uint32_t x = row_hash + (lb * 256u + pos + 1u) * 0x85EBCA77u;
+__host__ __device__ inline uint32_t drop_hash(uint32_t row_hash, uint32_t lb, uint32_t pos, uint32_t stride) {
+    uint32_t x = row_hash + (lb * stride + pos + 1u) * 0x85EBCA77u;
     x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
     return x;
 }
-__host__ __device__ inline float drop_factor(uint32_t row_hash, uint32_t lb, uint32_t pos, uint32_t thresh, float scale) {
-    return (drop_hash(row_hash, lb, pos) >> 8) >= thresh ? scale : 0.f;
+__host__ __device__ inline float drop_factor(uint32_t row_hash, uint32_t lb, uint32_t pos, uint32_t stride, uint32_t thresh, float scale) {
+    return (drop_hash(row_hash, lb, pos, stride) >> 8) >= thresh ? scale : 0.f;
 }
 
 int build_pack_map(const FlowPlan& L, int32_t* map);

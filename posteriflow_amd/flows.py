@@ -743,19 +743,20 @@ class NSFPosteriorFlow(nn.Module):
             raise NotImplementedError(
                 f"NSFPosteriorFlow(H={self.hidden_features}, D={self.features}, K={self.num_bins}): the generic-shape kernel "
                 "evaluates densities and samples for this shape; its backward (fp32 data-gradient chain) needs "
-                "H in {64, 128, 192, 256, 384, 512}, D <= 16, K <= 32, a plain conditioner and no conditioner dropout -- call "
+                "H in {64, 128, 192, 256, 384, 512}, D <= 16 and K <= 32 (either conditioner, with or without dropout) -- call "
                 "under torch.no_grad() or freeze the parameters")
         return need
 
     def _generic_trainable(self) -> bool:
-        """generic shapes the fp32 backward chain covers (csrc/pf_flow_bwd_chain.hip: H = 384 / 512 and K <= 32 in fp32)"""
-        return (self.hidden_features in (64, 128, 192, 256, 384, 512) and self.features <= 16 and self.num_bins <= 32
-                and not (self.dropout and self.dropout > 0.0))
+        """generic shapes the fp32 backward chain covers (csrc/pf_flow_bwd_chain.hip: H = 384 / 512 and K <= 32 in fp32), with
+        or without conditioner dropout (the generic kernel's training forward, flow_generic_kernel<.., 0, true>)"""
+        return self.hidden_features in (64, 128, 192, 256, 384, 512) and self.features <= 16 and self.num_bins <= 32
 
     # ---- conditioner dropout (train mode) ---------------------------------------------
     # nflows drops relu(W0 relu(h) + b0) inside every residual block while the module is in train mode (upstream
     # MaskedResidualBlock.forward, built at flows.py:510-524 with dropout_probability=dropout; the reference's own
-    # masked-context block does the same, flows.py:225-234).  The training forward kernel (flow_train_kernel) applies
+    # masked-context block does the same, flows.py:225-234).  The training forward kernel (flow_train_kernel; generic shapes:
+    # the DROP variant of flow_generic_kernel, with a counter stride of 512 above H = 256) applies
     # it from a counter hash of a per-call seed; the backward regenerates the factors (pf_flow_dropout_mask).
     def _drop_active(self) -> bool:
         return bool(self.training and self.dropout and self.dropout > 0.0)

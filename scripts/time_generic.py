@@ -39,3 +39,18 @@ for prec in ("fp32", "bf16"):
                   f"{draws / res[inc] / 1e3:.3f} M draws/s")
         flow.incremental_inverse = None
         print(f"{prec}: {draws} draws: incremental / d-pass = {res[False] / res[None]:.2f}x")
+# training step of the head on frozen contexts (forward with the layer inputs kept + fp32 backward) at 2048 rows, without and with
+# the reference's conditioner dropout (create_flow_model's default 0.15), both in one run
+for p in flow.parameters(): p.requires_grad_(True)
+flow.train()
+xt, ct = x[:2048], ctx[:2048]
+def step():
+    flow.zero_grad(set_to_none=True)
+    flow.compute_psd_aware_nll(xt, ct, None).mean().backward()
+for prec in ("fp32", "bf16"):
+    flow.precision = prec
+    ms = {}
+    for flow.dropout in (0.0, 0.15):
+        ms[flow.dropout] = median_ms(step)
+    print(f"{prec}: training forward + backward, 2048 rows: {ms[0.0]:.3f} ms without dropout, {ms[0.15]:.3f} ms with p = 0.15 "
+          f"({ms[0.15] / ms[0.0]:.3f}x)")
