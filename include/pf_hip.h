@@ -111,7 +111,8 @@ typedef struct PfFlowDesc {
  * pf_flow_backward_chain and pf_flow_rqs_backward.  The incremental-inverse, large-batch and bf16 backward entry points return
  * PF_ERR_UNSUPPORTED for such a shape.
  * Masked-context conditioner (PF_FLAG_MASKED_CONTEXT): forward / inverse on the scheduled kernels (context projections
- * hoisted) or the generic kernel; backward through the SAME fp32 entry points in their additive form -- pf_flow_reevaluate
+ * hoisted) or the generic kernel; sampling also through pf_flow_inverse_inc (both incremental kernels in their additive
+ * form, the shapes and precisions of the plain conditioner); backward through the SAME fp32 entry points in their additive form -- pf_flow_reevaluate
  * (fp32 desc, PF_FLAG_GENERIC | PF_FLAG_MASKED_CONTEXT layout; gates = NULL) and pf_flow_backward_chain (fp32 desc with the
  * flag; t2s = gates = NULL, Gc[l][1 + j] = dL/d(block j's context projection) = Gt1[j][l]). */
 
@@ -329,6 +330,12 @@ int pf_flow_inverse(const PfFlowDesc* desc, const void* packed,
  *   [D][96].  pf_flow_inc_layer_bytes = (H/16 + 4 (H/16) HK + T D HK) * 1024 + (5 H + 16 T D) * 4 with HK = H / 32 (bf16) or
  *   H / 16 (fp32) fragments per tile row and T = 3 (K <= 16) or 6 tail tiles per feature; -1 outside the two kernels' domain.
  *   PF_ERR_UNSUPPORTED (use pf_flow_inverse): fp32 at H > 384, D > 16, more than 8 new sixteen-unit tiles in one pass.
+ * PF_FLAG_MASKED_CONTEXT in desc->reserved (the only flag this entry point reads) selects the additive form of both kernels:
+ *   block j computes t1 = W1 relu(h) + b1 + ctx_proj[.][l][1 + j], h += W2 relu(t1) + b2 (no gate), slot 0 stays the
+ *   MADE-level relu(context_layer) term, and there is no ReversePermutation between the layers.  Same layer block, same
+ *   ctx_proj layout (the caller folds a full_context=False mask into the projection weights), same shape limits; the flag
+ *   needs context_features >= 1 and ctx_proj != NULL (PF_ERR_BAD_ARG otherwise).  Without the flag a non-NULL ctx_proj is
+ *   read as the GLU conditioner's projections.
  * z, x, logdet, fail_flags, ar_inv_perm, ctx_rows as in pf_flow_inverse. */
 int pf_pack_bf16_frags(const float* src, int32_t n_rows, int32_t k, void* out, void* stream);
 int64_t pf_flow_inc_layer_bytes(const PfFlowDesc* desc);

@@ -24,10 +24,10 @@ int fusion_forward(const char* packed, float* tokens, int n_tokens, const float*
 int inc_pack_frags(const float* src, int n_rows, int k, void* out, hipStream_t s);
 int64_t inc_layer_bytes(int D, int H, bool f32);
 int64_t inc_wide_layer_bytes(int D, int H, int K, bool f32);
-int flow_inverse_inc_wide(const PfFlowDesc& d, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
-                          int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x, float* logdet,
-                          uint32_t* fail, hipStream_t s);
-int flow_inverse_inc(const PfFlowDesc& d, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
+int flow_inverse_inc_wide(const PfFlowDesc& d, bool additive, float deriv_const, const int32_t* u1, const void* packed,
+                          const float* proj, int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x,
+                          float* logdet, uint32_t* fail, hipStream_t s);
+int flow_inverse_inc(const PfFlowDesc& d, bool additive, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
                      int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x, float* logdet,
                      uint32_t* fail, hipStream_t s);
 int64_t remix_workspace_bytes(int64_t batch);
@@ -459,6 +459,12 @@ int pf_flow_inverse_inc(const PfFlowDesc* desc, const int32_t* units_upto_degree
     if (batch < 0) return fail(PF_ERR_BAD_ARG, "negative batch");
     if (batch == 0) return PF_OK;
     if (!units_upto_degree || !packed || !z || !x) return fail(PF_ERR_BAD_ARG, "null pointer");
+    // the masked-context conditioner (additive instantiations of both kernels) is nothing without its projections
+    const bool additive = (desc->reserved & PF_FLAG_MASKED_CONTEXT) != 0;
+    if (additive && desc->context_features < 1)
+        return fail(PF_ERR_BAD_ARG, "incremental inverse: PF_FLAG_MASKED_CONTEXT needs context_features >= 1");
+    if (additive && !ctx_proj)
+        return fail(PF_ERR_BAD_ARG, "incremental inverse: PF_FLAG_MASKED_CONTEXT needs ctx_proj (the three additive context projections per layer)");
     if (ctx_proj && (ctx_rows < 1 || batch % ctx_rows != 0)) return fail(PF_ERR_BAD_ARG, "ctx_rows must be >= 1 and divide batch");
     if (misaligned(packed, 16) || misaligned(ctx_proj, 16)) return fail(PF_ERR_BAD_ARG, "packed / ctx_proj must be 16-byte aligned");
     if (units_upto_degree[0] != 0 || units_upto_degree[D] > H) return fail(PF_ERR_BAD_ARG, "units_upto_degree[0] must be 0 and [D] <= H");
@@ -466,7 +472,7 @@ int pf_flow_inverse_inc(const PfFlowDesc* desc, const int32_t* units_upto_degree
         if (units_upto_degree[i] > units_upto_degree[i + 1]) return fail(PF_ERR_BAD_ARG, "units_upto_degree must be non-decreasing");
     const float dc = (float)std::log(std::exp(1.0 - (double)desc->min_derivative) - 1.0);
     const int rc = (wide ? pf::flow_inverse_inc_wide : pf::flow_inverse_inc)(
-        *desc, dc, units_upto_degree, packed, ctx_proj, ctx_proj ? ctx_rows : batch, z, ar_inv_perm, batch, x, logdet, fail_flags,
+        *desc, additive, dc, units_upto_degree, packed, ctx_proj, ctx_proj ? ctx_rows : batch, z, ar_inv_perm, batch, x, logdet, fail_flags,
         static_cast<hipStream_t>(stream));
     if (rc == PF_ERR_UNSUPPORTED) return fail(rc, "incremental inverse: more than 8 sixteen-unit tiles hold the units of one degree");
     return rc == PF_OK ? rc : fail(rc, hipGetErrorString(static_cast<hipError_t>(pf::g_hip_error)));

@@ -75,10 +75,16 @@ constexpr int kActStrideF32 = 256 * 4;
 // kF32: the fp32 parity mode.  fp32 weights and activations, v_mfma_f32_16x16x4_f32: a fragment is 16 units x 16 k
 // (lane (r, kq) holds W[r][16 q + 4 kq .. + 3], one dwordx4; B = 4 consecutive floats of the activation row), 16
 // fragments per tile row at H = 256, activation rows of 1024 bytes (80 KB of LDS state: one workgroup per CU).
-template <int kCols, int kThreads, bool kCtx, bool kF32>
+// kAdd (needs kCtx): the masked-context conditioner (oracle/nflows_restated.py:198-263).  The blocks have no gate: projection
+// slot 1 + j is ADDED in front of block j's inner relu (stages b / d), stages c / e are plain residual adds, and there is
+// no ReversePermutation between the layers.  The loads and their stages are those of the GLU form: P(1) arrives with the
+// head of the pass and is used in stage b (one stage later than its request instead of two), P(2) is requested in stage c
+// and used in stage d; the exponentials of the two sigmoids are gone.
+template <int kCols, int kThreads, bool kCtx, bool kF32, bool kAdd = false>
 __global__ __launch_bounds__(kThreads)
 __attribute__((amdgpu_waves_per_eu(kThreads == 256 && !kF32 ? 3 : 1, kThreads == 256 && !kF32 ? 3 : 2)))
 void flow_inverse_inc_kernel(const IncParams p) {
+    static_assert(kCtx || !kAdd, "the additive conditioner has context by definition");
     constexpr int kRows = 16 * kCols;
     constexpr int NF = kF32 ? 16 : 8;                            // fragments (k-steps of 16 / 32) per tile row, at most
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -314,17 +320,19 @@ void flow_inverse_inc_kernel(const IncParams p) {
             }
             __syncthreads();
             PF_TR(1);
-            if (mine) {                                                             // ---- stage b: act1 = relu(W1 . act0 + b1)
+            if (mine) {                                                             // ---- stage b: act1 = relu(W1 . act0 + b1 [+ pg0: kAdd])
                 fetch(Y, p.off_w2[0], t, kmax);
                 bY = *reinterpret_cast<const f32x4*>(bias + 2 * H + u);
                 gemm(X, act_of(0), kmax, v);
 #pragma unroll
-                for (int cc = 0; cc < kCols; ++cc)
-                    put(1, cc, u, relu4(v[cc] + bX));
+                for (int cc = 0; cc < kCols; ++cc) {
+                    if constexpr (kAdd) put(1, cc, u, relu4(v[cc] + bX + pg0[cc]));
+                    else put(1, cc, u, relu4(v[cc] + bX));
+                }
             }
             __syncthreads();
             PF_TR(2);
-            if (mine) {                                                             // ---- stage c: h1 = h0 + (W2 . act1 + b2) sigmoid(pg0)
+            if (mine) {                                                             // ---- stage c: h1 = h0 + (W2 . act1 + b2) sigmoid(pg0)  (kAdd: no gate)
                 fetch(X, p.off_w1[1], t, kmax);
                 bX = *reinterpret_cast<const f32x4*>(bias + 3 * H + u);
                 if constexpr (kCtx) {
@@ -336,20 +344,22 @@ void flow_inverse_inc_kernel(const IncParams p) {
 #pragma unroll
                 for (int cc = 0; cc < kCols; ++cc) {
                     f32x4 d = v[cc] + bY;
-                    if constexpr (kCtx) d = d * sigmoid4<!kF32>(pg0[cc]);
+                    if constexpr (kCtx && !kAdd) d = d * sigmoid4<!kF32>(pg0[cc]);
                     h[cc] = h[cc] + d;
                     put(2, cc, u, relu4(h[cc]));
                 }
             }
             __syncthreads();
             PF_TR(3);
-            if (mine) {                                                             // ---- stage d
+            if (mine) {                                                             // ---- stage d  (kAdd: + pg1, requested in stage c)
                 fetch(Y, p.off_w2[1], t, kmax);
                 bY = *reinterpret_cast<const f32x4*>(bias + 4 * H + u);
                 gemm(X, act_of(2), kmax, v);
 #pragma unroll
-                for (int cc = 0; cc < kCols; ++cc)
-                    put(3, cc, u, relu4(v[cc] + bX));
+                for (int cc = 0; cc < kCols; ++cc) {
+                    if constexpr (kAdd) put(3, cc, u, relu4(v[cc] + bX + pg1[cc]));
+                    else put(3, cc, u, relu4(v[cc] + bX));
+                }
             }
             __syncthreads();
             PF_TR(4);
@@ -357,12 +367,12 @@ void flow_inverse_inc_kernel(const IncParams p) {
             // fetch of Y and its use
             fetch(X, p.off_wf, 3 * i + wf, wave < 3 ? kmax : 0);
             bX = *reinterpret_cast<const f32x4*>(bias + 5 * H + 48 * i + 16 * wf + 4 * g);
-            if (mine) {                                                             // ---- stage e: h2 = h1 + (W2 . act3 + b2) sigmoid(pg1)
+            if (mine) {                                                             // ---- stage e: h2 = h1 + (W2 . act3 + b2) sigmoid(pg1)  (kAdd: no gate)
                 gemm(Y, act_of(3), kmax, v);
 #pragma unroll
                 for (int cc = 0; cc < kCols; ++cc) {
                     f32x4 d = v[cc] + bY;
-                    if constexpr (kCtx) d = d * sigmoid4<!kF32>(pg1[cc]);
+                    if constexpr (kCtx && !kAdd) d = d * sigmoid4<!kF32>(pg1[cc]);
                     h[cc] = h[cc] + d;
                     put(4, cc, u, h[cc]);
                 }
@@ -381,10 +391,11 @@ void flow_inverse_inc_kernel(const IncParams p) {
             pass(i, bufB, bB, bufA, bA);
             if (i + 1 < D) pass(i + 1, bufA, bA, bufB, bB);
         }
-        // this layer's input is the previous layer's output, reversed (ReversePermutation precedes every layer)
+        // this layer's input is the previous layer's output, reversed (ReversePermutation precedes every layer; the
+        // masked-context flow has none)
         for (int s = tid; s < kRows * 16; s += kThreads) {
             const int r = s >> 4, d = s & 15;
-            ys[s] = d < D ? xs[r * 16 + (D - 1 - d)] : 0.f;
+            ys[s] = d < D ? xs[r * 16 + (kAdd ? d : D - 1 - d)] : 0.f;
         }
         __syncthreads();
     }
@@ -426,7 +437,8 @@ int64_t inc_layer_bytes(int D, int H, bool f32) {
     return (NT + 4 * NT * HK + 3 * (int64_t)D * HK) * 1024 + (5 * (int64_t)H + 48 * (int64_t)D) * 4;
 }
 
-int flow_inverse_inc(const PfFlowDesc& d, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
+// additive: the masked-context conditioner's instantiations (the caller has checked that proj is there)
+int flow_inverse_inc(const PfFlowDesc& d, bool additive, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
                      int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x, float* logdet,
                      uint32_t* fail, hipStream_t s) {
     IncParams p{};
@@ -458,11 +470,12 @@ int flow_inverse_inc(const PfFlowDesc& d, float deriv_const, const int32_t* u1, 
     if (force512) threads = 512;                     // (tuning knob, read once per process)
     const size_t lds = 5 * 16 * (size_t)(f32 ? kActStrideF32 : kActStride) + 16 * 64 + 16 * (16 + 16 + kParS + 2) * 4;
     using Kern = void (*)(const IncParams);
-    static const Kern kerns[8] = {
-        flow_inverse_inc_kernel<1, 256, false, false>, flow_inverse_inc_kernel<1, 256, true, false>,
-        flow_inverse_inc_kernel<1, 512, false, false>, flow_inverse_inc_kernel<1, 512, true, false>,
-        flow_inverse_inc_kernel<1, 256, false, true>,  flow_inverse_inc_kernel<1, 256, true, true>,
-        flow_inverse_inc_kernel<1, 512, false, true>,  flow_inverse_inc_kernel<1, 512, true, true>};
+    // [precision][threads][none | GLU context | additive context]
+    static const Kern kerns[12] = {
+        flow_inverse_inc_kernel<1, 256, false, false>, flow_inverse_inc_kernel<1, 256, true, false>, flow_inverse_inc_kernel<1, 256, true, false, true>,
+        flow_inverse_inc_kernel<1, 512, false, false>, flow_inverse_inc_kernel<1, 512, true, false>, flow_inverse_inc_kernel<1, 512, true, false, true>,
+        flow_inverse_inc_kernel<1, 256, false, true>,  flow_inverse_inc_kernel<1, 256, true, true>,  flow_inverse_inc_kernel<1, 256, true, true, true>,
+        flow_inverse_inc_kernel<1, 512, false, true>,  flow_inverse_inc_kernel<1, 512, true, true>,  flow_inverse_inc_kernel<1, 512, true, true, true>};
     // the opt-in to > 64 KB of dynamic LDS is a per-DEVICE function attribute: remember it per device, under a lock
     {
         static std::mutex mu;
@@ -477,7 +490,8 @@ int flow_inverse_inc(const PfFlowDesc& d, float deriv_const, const int32_t* u1, 
             configured[devid] = true;
         }
     }
-    const int variant = (f32 ? 4 : 0) + (threads == 256 ? 0 : 2) + (proj ? 1 : 0);
+    if (additive && !proj) return PF_ERR_BAD_ARG;
+    const int variant = (f32 ? 6 : 0) + (threads == 256 ? 0 : 3) + (proj ? (additive ? 2 : 1) : 0);
     const bool tracing = std::getenv("PF_INC_TRACE") != nullptr;
     if (tracing && hipMalloc(&p.trace, p.L * 16 * 8 * sizeof(unsigned long long)) != hipSuccess) return PF_ERR_HIP;
     const dim3 grid(static_cast<unsigned>((batch + 15) / 16));

@@ -15,7 +15,8 @@ constexpr int kParS = kParStride;          // floats per row in the spline-param
 struct IncParams {
     FwdParams sp;              // spline scalars only: tail_bound, min_w, min_h, min_d, deriv_const
     const char* w;             // L layer blocks (see pf_hip.h, pf_flow_inverse_inc)
-    const float* proj;         // [ctx_rows][L][3][H] fp32 in sorted-unit order, or null when C = 0
+    const float* proj;         // [ctx_rows][L][3][H] fp32 in sorted-unit order, or null when C = 0: slot 0 = the MADE-level context
+                               // layer, slots 1 / 2 = the blocks' gates (GLU) or additive projections (kAdd, masked context)
     const float* z;            // [batch][D]
     float* x;                  // [batch][D]
     float* logdet;             // [batch] or null

@@ -113,10 +113,13 @@ constexpr size_t wide_lds_bytes(int units, bool f32, bool k32) {
     return (size_t)5 * kRows * units * (f32 ? 4 : 2) + kRows * 64 + kRows * (16 + 16 + (k32 ? kParS32 : kParS) + 2) * 4;
 }
 
-// kUnits: activation-row stride in units (>= H); kK32: K > 16 (six tail tiles, 32 lanes per draw)
-template <int kUnits, bool kCtx, bool kF32, bool kK32>
+// kUnits: activation-row stride in units (>= H); kK32: K > 16 (six tail tiles, 32 lanes per draw); kAdd (needs kCtx): the
+// masked-context conditioner, as in pf_flow_inc.hip -- projection slot 1 + j added in front of block j's inner relu (stages
+// b / d, each one stage behind its request), plain residual adds in stages c / e, no ReversePermutation between layers
+template <int kUnits, bool kCtx, bool kF32, bool kK32, bool kAdd = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void flow_inverse_inc_wide_kernel(const IncParams p) {
+    static_assert(kCtx || !kAdd, "the additive conditioner has context by definition");
     constexpr int NF = kF32 ? kUnits / 16 : kUnits / 32;         // fragments (k-steps of 16 / 32) per tile row, at most
     constexpr int AS = kUnits * (kF32 ? 4 : 2);                  // bytes per activation row: NF / 4 bank windows of 256 bytes
     constexpr int PS = kK32 ? kParS32 : kParS;                   // floats per spline-parameter row
@@ -313,35 +316,37 @@ void flow_inverse_inc_wide_kernel(const IncParams p) {
                 put(0, u, relu4(w0));
             }
             __syncthreads();
-            if (mine) {                                                             // ---- stage b: act1 = relu(W1 . act0 + b1)
+            if (mine) {                                                             // ---- stage b: act1 = relu(W1 . act0 + b1 [+ pg0: kAdd])
                 fetch(Y, p.off_w2[0], t, kmax);
                 bY = *reinterpret_cast<const f32x4*>(bias + 2 * H + u);
-                put(1, u, relu4(gemm(X, act_of(0), kmax) + bX));
+                if constexpr (kAdd) put(1, u, relu4(gemm(X, act_of(0), kmax) + bX + pg0));
+                else put(1, u, relu4(gemm(X, act_of(0), kmax) + bX));
             }
             __syncthreads();
-            if (mine) {                                                             // ---- stage c: h1 = h0 + (W2 . act1 + b2) sigmoid(pg0)
+            if (mine) {                                                             // ---- stage c: h1 = h0 + (W2 . act1 + b2) sigmoid(pg0)  (kAdd: no gate)
                 fetch(X, p.off_w1[1], t, kmax);
                 bX = *reinterpret_cast<const f32x4*>(bias + 3 * H + u);
                 if constexpr (kCtx) pg1 = proj_load(l, 2, u);
                 f32x4 d = gemm(Y, act_of(1), kmax) + bY;
-                if constexpr (kCtx) d = d * sigmoid4<!kF32>(pg0);
+                if constexpr (kCtx && !kAdd) d = d * sigmoid4<!kF32>(pg0);
                 h = h + d;
                 put(2, u, relu4(h));
             }
             __syncthreads();
-            if (mine) {                                                             // ---- stage d
+            if (mine) {                                                             // ---- stage d  (kAdd: + pg1, requested in stage c)
                 fetch(Y, p.off_w2[1], t, kmax);
                 bY = *reinterpret_cast<const f32x4*>(bias + 4 * H + u);
-                put(3, u, relu4(gemm(X, act_of(2), kmax) + bX));
+                if constexpr (kAdd) put(3, u, relu4(gemm(X, act_of(2), kmax) + bX + pg1));
+                else put(3, u, relu4(gemm(X, act_of(2), kmax) + bX));
             }
             __syncthreads();
             // stage f's weights, one stage ahead; unconditional (an empty resource for waves without a tail tile): it sits
             // between the fetch of Y and its use
             fetch(X, p.off_wf, NTAIL * i + wf, wave < NTAIL ? kmax : 0);
             bX = *reinterpret_cast<const f32x4*>(bias + 5 * H + 16 * NTAIL * i + 16 * wf + 4 * g);
-            if (mine) {                                                             // ---- stage e: h2 = h1 + (W2 . act3 + b2) sigmoid(pg1)
+            if (mine) {                                                             // ---- stage e: h2 = h1 + (W2 . act3 + b2) sigmoid(pg1)  (kAdd: no gate)
                 f32x4 d = gemm(Y, act_of(3), kmax) + bY;
-                if constexpr (kCtx) d = d * sigmoid4<!kF32>(pg1);
+                if constexpr (kCtx && !kAdd) d = d * sigmoid4<!kF32>(pg1);
                 h = h + d;
                 put(4, u, h);
             }
@@ -357,10 +362,11 @@ void flow_inverse_inc_wide_kernel(const IncParams p) {
             pass(i, bufB, bB, bufA, bA);
             if (i + 1 < D) pass(i + 1, bufA, bA, bufB, bB);
         }
-        // this layer's input is the previous layer's output, reversed (ReversePermutation precedes every layer)
+        // this layer's input is the previous layer's output, reversed (ReversePermutation precedes every layer; the
+        // masked-context flow has none)
         for (int s = tid; s < kRows * 16; s += kThreads) {
             const int r = s >> 4, d = s & 15;
-            ys[s] = d < D ? xs[r * 16 + (D - 1 - d)] : 0.f;
+            ys[s] = d < D ? xs[r * 16 + (kAdd ? d : D - 1 - d)] : 0.f;
         }
         __syncthreads();
     }
@@ -381,8 +387,9 @@ void flow_inverse_inc_wide_kernel(const IncParams p) {
 using WideKern = void (*)(const IncParams);
 struct WideVariant { WideKern k; size_t lds; };
 template <int kUnits, bool kF32, bool kK32>
-WideVariant wide_variant(bool ctx) {
-    return {ctx ? flow_inverse_inc_wide_kernel<kUnits, true, kF32, kK32> : flow_inverse_inc_wide_kernel<kUnits, false, kF32, kK32>,
+WideVariant wide_variant(bool ctx, bool add) {
+    return {add ? flow_inverse_inc_wide_kernel<kUnits, true, kF32, kK32, true>
+                : ctx ? flow_inverse_inc_wide_kernel<kUnits, true, kF32, kK32> : flow_inverse_inc_wide_kernel<kUnits, false, kF32, kK32>,
             wide_lds_bytes(kUnits, kF32, kK32)};
 }
 }  // namespace
@@ -397,7 +404,7 @@ int64_t inc_wide_layer_bytes(int D, int H, int K, bool f32) {
 // PF_ERR_UNSUPPORTED: fp32 at H > 384 (five fp32 stages of 16 rows x 512 units are the whole 160 KB of LDS), or more than
 // 8 sixteen-unit tiles holding the units of one degree (a wave owns one new tile per pass).  The caller (pf_api.hip) has
 // checked H, K and D.
-int flow_inverse_inc_wide(const PfFlowDesc& d, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
+int flow_inverse_inc_wide(const PfFlowDesc& d, bool additive, float deriv_const, const int32_t* u1, const void* packed, const float* proj,
                           int64_t ctx_rows, const float* z, const int32_t* inv_perm, int64_t batch, float* x, float* logdet,
                           uint32_t* fail, hipStream_t s) {
     IncParams p{};
@@ -406,7 +413,8 @@ int flow_inverse_inc_wide(const PfFlowDesc& d, float deriv_const, const int32_t*
     p.w = static_cast<const char*>(packed); p.proj = proj; p.z = z; p.x = x; p.logdet = logdet; p.fail = fail;
     p.inv_perm = inv_perm; p.batch = batch; p.ctx_rows = ctx_rows;
     p.D = d.features; p.H = d.hidden_features; p.K = d.num_bins; p.L = d.num_layers;
-    const bool f32 = d.precision == PF_PREC_F32, k32 = p.K > 16, ctx = proj != nullptr;
+    const bool f32 = d.precision == PF_PREC_F32, k32 = p.K > 16, ctx = proj != nullptr, add = additive;
+    if (add && !ctx) return PF_ERR_BAD_ARG;                      // (the additive instantiations read the projections)
     if (f32 && p.H > 384) return PF_ERR_UNSUPPORTED;
     int max_tiles = 0;
     for (int i = 1; i < p.D; ++i) max_tiles = std::max(max_tiles, (u1[i] + 15) / 16 - u1[i - 1] / 16);
@@ -423,11 +431,11 @@ int flow_inverse_inc_wide(const PfFlowDesc& d, float deriv_const, const int32_t*
     for (int i = 0; i <= p.D; ++i) p.u1[i] = u1[i];
     // the row stride is the smallest instantiated one that holds H; H <= 256 comes here only with K > 16
     WideVariant v;
-    if (p.H <= 256) v = f32 ? wide_variant<256, true, true>(ctx) : wide_variant<256, false, true>(ctx);
+    if (p.H <= 256) v = f32 ? wide_variant<256, true, true>(ctx, add) : wide_variant<256, false, true>(ctx, add);
     else if (p.H <= 384)
-        v = f32 ? (k32 ? wide_variant<384, true, true>(ctx) : wide_variant<384, true, false>(ctx))
-                : (k32 ? wide_variant<384, false, true>(ctx) : wide_variant<384, false, false>(ctx));
-    else v = k32 ? wide_variant<512, false, true>(ctx) : wide_variant<512, false, false>(ctx);
+        v = f32 ? (k32 ? wide_variant<384, true, true>(ctx, add) : wide_variant<384, true, false>(ctx, add))
+                : (k32 ? wide_variant<384, false, true>(ctx, add) : wide_variant<384, false, false>(ctx, add));
+    else v = k32 ? wide_variant<512, false, true>(ctx, add) : wide_variant<512, false, false>(ctx, add);
     // the opt-in to > 64 KB of dynamic LDS is a per-device function attribute: set before every launch, as the forward
     // kernels' launch_variant does
     if (v.lds > 64 * 1024 && !opt_in_lds(reinterpret_cast<const void*>(v.k), (int)v.lds)) return PF_ERR_HIP;

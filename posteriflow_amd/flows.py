@@ -875,7 +875,9 @@ class NSFPosteriorFlow(nn.Module):
 
     # ---- inverse / sampling ------------------------------------------------------------------
     # ---- incremental inverse: one masked conditioner evaluation per layer instead of D dense ones ----
-    incremental_inverse: Optional[bool] = None      # None: on for the plain conditioner (both precisions); False: D-pass kernel
+    incremental_inverse: Optional[bool] = None      # None: on for both conditioners (both precisions); False: D-pass kernel;
+                                                    # True: also for masked contexts wider than the default's limit below
+    masked_incremental_max_context = 300
 
     def _generic_shape(self) -> bool:
         """a shape outside the scheduled kernels' set (e.g. the 12 x 384 x 24 head of experiments/frozen_context_heads.py:
@@ -885,7 +887,15 @@ class NSFPosteriorFlow(nn.Module):
                     and 2 <= self.num_bins <= 16)
 
     def _use_incremental(self) -> bool:
-        if self.incremental_inverse is False or self.use_masked_context:
+        if self.incremental_inverse is False:
+            return False
+        # The masked-context conditioner runs the same two kernels in their additive form, under the same shape gates.  By
+        # default only up to the context widths its incremental path is tested and timed at (C <= 300: the reference's
+        # masked flows are 264 / 288 wide); wider masked contexts keep the D-pass default that
+        # tests/test_flow_context_width_gpu.py pins for them, and take the incremental kernels with incremental_inverse = True
+        # (the kernels themselves have no width limit: the projections arrive precomputed)
+        if self.use_masked_context and self.context_features > self.masked_incremental_max_context \
+                and self.incremental_inverse is not True:
             return False
         # scheduled shapes: csrc/pf_flow_inc.hip; H above 256 (up to 512) or K above 16 (up to 32): csrc/pf_flow_inc_wide.hip
         # (what that kernel refuses inside this range -- fp32 above H = 384, more than 8 new tiles in a pass -- comes back as
@@ -965,7 +975,9 @@ class NSFPosteriorFlow(nn.Module):
                 assert off + vec.numel() * 4 == (l + 1) * layer_bytes
                 buf[off:off + vec.numel() * 4].copy_(vec.view(torch.uint8))
                 if self.context_features > 0:
-                    wc.append(torch.stack([net.context_layer.weight[perm]] + [b.context_layer.weight[perm] for b in net.blocks]))
+                    # (masked context: a full_context=False mask is folded into the projection weights here, as for pf_flow_pack)
+                    cw = lambda m: m.masked_weight() if isinstance(m, _MaskedContextLinear) else m.weight
+                    wc.append(torch.stack([cw(net.context_layer)[perm]] + [cw(b.context_layer)[perm] for b in net.blocks]))
                     bc.append(torch.stack([net.context_layer.bias[perm]] + [b.context_layer.bias[perm] for b in net.blocks]))
             wfrags = bcat = None
             if wc:       # every layer's three context matrices as ONE packed GEMM operand [L * 3 * H][C] (sorted-unit rows)
